@@ -2,17 +2,22 @@
 """bench.py -- Hector scan-match + grid-update throughput on MI355X (BASELINE.json metric).
 
 One step = one HectorSlamProcessor::update (match coarse->fine + log-odds raycast update of every
-pyramid level) for each of B independent scan streams resident in HBM (inputs uploaded before the
-timed region).  Benchmark mode forces a map update on every scan (thresholds < 0).
+pyramid level) for each of B independent scan streams resident in HBM (the LaserScan ranges
+are generated on the device before the timed region, fill_device_ranges: seeded, a step's scans depend
+on the seed and the step alone).  Benchmark mode forces a map update on every scan (thresholds < 0).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--streams B] [--config northstar|c2|c3|gmapping|plicp|karto|karto_loop]
+                  [--full] [--dump-outputs DIR]
 
 Multi-GPU: launched by torch.distributed.run, one process per GPU; each rank runs its own B streams
 (replicas only -- the Hector path has no cross-stream exchange), barrier + synchronize around the
 timed region, max time over ranks, value = total scans of all ranks / that time.
 
-Rank 0 prints ONE JSON line with value, roofline (dominant kernel, HIP-event timed inside the timed
-region) and cpu_baseline (the CPU oracle, single core, bounded sample).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints value and
+ms_per_step.  --full adds everything else: roofline (dominant kernel, HIP-event timed in an instrumented
+pass after the timed region), the copy-bandwidth probe, cpu_baseline (the CPU oracle, one core and all
+cores, bounded samples), pose_vs_ref (the pose check against the oracle) and targets.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -150,6 +155,113 @@ def write_calibration():
             "ratios": ratios}
 
 
+DUMP_BUDGET_BYTES = 56 * 10 ** 6  # --dump-outputs writes at most this much array data (the files stay under 64 MB)
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(dirname: str, arrays: dict, rank: int = 0, world: int = 1) -> dict:
+    """--dump-outputs DIR: write `arrays` (name -> ndarray: what the timed path's last step handed its caller) as
+    DIR/<name>.npy (DIR/<name>_rank<r>.npy on the ranks of a multi-GPU job).  float32 stays float32, everything
+    else becomes float64 (exact for the int32 / int64 counts written here).  The arrays share DUMP_BUDGET_BYTES,
+    smallest first; one that does not fit in its share is cut to a fixed sample of its flattened elements (sorted
+    indices drawn without replacement by default_rng(DUMP_SAMPLE_SEED): the same cells in every run and every
+    build).  Returns name -> {"shape", "dtype", "sampled"}."""
+    os.makedirs(dirname, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        conv[name] = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+    left, info = DUMP_BUDGET_BYTES, {}
+    order = sorted(conv, key=lambda n: conv[n].nbytes)
+    for i, name in enumerate(order):
+        a = conv[name]
+        share = left // (len(order) - i)
+        sampled = a.nbytes > share
+        if sampled:
+            keep = max(share // a.itemsize, 1)
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        left -= a.nbytes
+        np.save(os.path.join(dirname, f"{name}.npy" if world == 1 else f"{name}_rank{rank}.npy"), a)
+        info[name] = {"shape": list(a.shape), "dtype": str(a.dtype), "sampled": bool(sampled)}
+    return info
+
+
+SCAN_NOISE_SIGMA = 0.01   # range noise of the synthetic scans, as synth.make_streams
+SCAN_PATHS = 64           # distinct base paths (stream s follows path s % SCAN_PATHS with its own noise)
+
+
+def stream_paths(num_streams: int, t_begin: int, t_end: int):
+    """Room-frame poses [paths][t_end - t_begin][3] of the streams' base paths (synth.trajectory, path p at phase
+    2 pi p / paths, as synth.make_streams) and the same poses in each path's first-pose frame (the streams'
+    ground truth)."""
+    from slam2d import synth
+
+    n_paths = min(SCAN_PATHS, num_streams)
+    poses, rel = [], []
+    for p in range(n_paths):
+        tr = synth.trajectory(t_end, 2.0 * math.pi * p / n_paths)
+        x0, y0, th0 = tr[0]
+        c, sn = math.cos(-th0), math.sin(-th0)
+        dx, dy = tr[:, 0] - x0, tr[:, 1] - y0
+        rel.append(np.stack([c * dx - sn * dy, sn * dx + c * dy,
+                             np.arctan2(np.sin(tr[:, 2] - th0), np.cos(tr[:, 2] - th0))], 1)[t_begin:])
+        poses.append(tr[t_begin:])
+    return np.stack(poses), np.stack(rel)
+
+
+def cast_ranges_device(poses: np.ndarray, dev, chunk: int = 256):
+    """synth.cast_ranges on the device: exact ranges [n][1081] (float64 tensor, inf when nothing within
+    RANGE_MAX) of the room's segments from `poses` [n][3], the same ray / segment intersection in float64."""
+    import torch
+
+    from slam2d import synth
+
+    segs = torch.from_numpy(synth.world_segments()).to(dev)
+    ang = torch.from_numpy(synth.beam_angles()).to(dev)
+    a, e = segs[:, 0, :], segs[:, 1, :] - segs[:, 0, :]
+    inf = torch.tensor(float("inf"), dtype=torch.float64, device=dev)
+    out = torch.empty((poses.shape[0], ang.shape[0]), dtype=torch.float64, device=dev)
+    for c in range(0, poses.shape[0], chunk):
+        p = torch.from_numpy(np.ascontiguousarray(poses[c:c + chunk])).to(dev)
+        th = p[:, 2:3] + ang[None, :]
+        dx, dy = torch.cos(th)[:, :, None], torch.sin(th)[:, :, None]        # [n, beams, 1]
+        den = dx * e[:, 1] - dy * e[:, 0]                                    # [n, beams, segments]
+        wx = (a[None, :, 0] - p[:, 0:1])[:, None, :]
+        wy = (a[None, :, 1] - p[:, 1:2])[:, None, :]
+        t = (wx * e[:, 1] - wy * e[:, 0]) / den
+        u = (wx * dy - wy * dx) / den
+        ok = (den.abs() > 1e-12) & (t > 1e-9) & (u >= 0.0) & (u <= 1.0)
+        r = torch.where(ok, t, inf).amin(dim=2)
+        out[c:c + chunk] = torch.where(r > synth.RANGE_MAX, inf, r)
+    return out
+
+
+def fill_device_ranges(d_rng, t_begin: int, seed: int):
+    """Fill d_rng (float32 device tensor [steps][streams][1081]) with the LaserScan ranges of steps t_begin ...
+    t_begin + steps - 1, generated on the device: stream s follows base path s % SCAN_PATHS (cast_ranges_device)
+    plus N(0, SCAN_NOISE_SIGMA) range noise of its own.  The noise of step t is one float64 draw [streams][1081] of a
+    generator seeded with seed * 1000003 + t, so a step's scans depend on (seed, t) alone: the same in every run,
+    whatever the number of steps, and a buffer can be refilled with later steps.  Returns the ground truth
+    [paths][steps][3] (first-pose frame)."""
+    import torch
+
+    steps, B, nb = d_rng.shape
+    dev = d_rng.device
+    poses, rel = stream_paths(B, t_begin, t_begin + steps)
+    n_paths = poses.shape[0]
+    base = cast_ranges_device(poses.reshape(-1, 3), dev).reshape(n_paths, steps, nb)
+    path_of = torch.arange(B, device=dev) % n_paths
+    inf = torch.tensor(float("inf"), dtype=torch.float64, device=dev)
+    g = torch.Generator(device=dev)
+    for k in range(steps):
+        g.manual_seed(seed * 1000003 + t_begin + k)
+        noise = torch.randn((B, nb), generator=g, dtype=torch.float64, device=dev)
+        b = base[:, k].index_select(0, path_of)
+        d_rng[k] = torch.where(torch.isfinite(b), b + SCAN_NOISE_SIGMA * noise, inf)
+    return rel
+
+
 def aggregate_over_ranks(elapsed: float, units: float, device):
     """Whole-job timing: the slowest rank's time (MAX) and the units all ranks processed (SUM).
     Works on any backend (RCCL on the GPU box, gloo in the CPU tests)."""
@@ -236,8 +348,8 @@ def cpu_baseline(cfg, seconds=10.0, seconds_o0=4.0, thresholds=(-1.0, -1.0)):
 
 def hector_cpu_block(args, cfg, thr, seconds=10.0, seconds_o0=4.0, seconds_all=6.0):
     """The line's cpu_baseline at EVERY GPU count (north_star: the reference CPU path timed "in the same run"):
-    rank 0 alone runs it, after the timed region, on 1 core and then on --cpu-cores processes."""
-    if args.no_cpu_baseline:
+    rank 0 alone runs it, after the timed region, on 1 core and then on --cpu-cores processes (--full only)."""
+    if not args.full or args.no_cpu_baseline:
         return None
     cpu = cpu_baseline(cfg, seconds=seconds, seconds_o0=seconds_o0, thresholds=thr)
     if args.cpu_cores > 1:
@@ -279,18 +391,28 @@ def cpu_baseline_all_cores(cfg, procs, seconds=6.0, thresholds=(-1.0, -1.0)):
                       "oracle -O3"}
 
 
-def pose_check(cfg, S, gpu_poses, streams, thresholds=(-1.0, -1.0), order=0):
+def pose_check(cfg, S, gpu_poses, streams, thresholds=(-1.0, -1.0), order=0, log_ranges=None, log_gt=None,
+               num_streams=None):
     """Pose error of the logged GPU streams (device pose log slot i = stream streams[i], every step incl.
     warmup) vs the CPU oracle in the reference's sequential summation order on the same scans -- the
     metric's 'pose RMSE vs ref' -- plus the absolute error against the synthetic ground truth.
     order: the kernel's Hessian summation order (0 = the reference's, the default: the poses must then
-    equal the oracle's bit for bit; 256 = the opt-in tree, also compared with the oracle in that order)."""
+    equal the oracle's bit for bit; 256 = the opt-in tree, also compared with the oracle in that order).
+    The scans are S's points, or (ranges input) log_ranges [logged stream][scan][1081], the ranges the device was
+    given, converted as the node does (synth.ranges_to_points), with log_gt [logged stream][scan][3].  The
+    streams are independent, so they are replayed on up to 16 threads (the oracle runs outside the GIL)."""
     sys.path.insert(0, os.path.join(REPO, "oracle"))
+    from concurrent.futures import ThreadPoolExecutor
+
     import oracle as O
+    from slam2d import synth
 
     n_scans = gpu_poses.shape[0]
-    e, egt, etree = [], [], []
-    for i, s in enumerate(streams):
+    num_streams = num_streams or S.points.shape[0]
+
+    def replay(item):
+        i, s = item
+        e, egt, etree = [], [], []
         r = O.HectorOracle(0.05, cfg["map_size"], (0.5, 0.5), cfg["levels"], reduce_threads=0)
         rt = O.HectorOracle(0.05, cfg["map_size"], (0.5, 0.5), cfg["levels"], reduce_threads=order) if order else None
         for h in (r, rt):
@@ -298,17 +420,26 @@ def pose_check(cfg, S, gpu_poses, streams, thresholds=(-1.0, -1.0), order=0):
                 h.set_update_factors(0.4, 0.9)
                 h.set_thresholds(*thresholds)
         for k in range(n_scans):
-            pts = S.points[s, k, : S.counts[s, k]]
+            if log_ranges is not None:
+                pts = synth.ranges_to_points(log_ranges[i, k].astype(np.float64))[0]
+            else:
+                pts = S.points[s, k, : S.counts[s, k]]
             rp, _, _ = r.process(pts)
             e.append(gpu_poses[k, i].astype(np.float64) - rp.astype(np.float64))
             if rt is not None:
                 tp, _, _ = rt.process(pts)
                 etree.append(gpu_poses[k, i].astype(np.float64) - tp.astype(np.float64))
-            egt.append(gpu_poses[k, i].astype(np.float64) - S.gt[s, k])
+            egt.append(gpu_poses[k, i].astype(np.float64) - (log_gt[i, k] if log_gt is not None else S.gt[s, k]))
         r.close()
         if rt is not None:
             rt.close()
-    e, egt = np.asarray(e), np.asarray(egt)
+        return e, egt, etree
+
+    with ThreadPoolExecutor(max(1, min(16, os.cpu_count() or 1, len(streams)))) as ex:
+        parts = list(ex.map(replay, enumerate(streams)))
+    e = np.asarray([x for p in parts for x in p[0]])
+    egt = np.asarray([x for p in parts for x in p[1]])
+    etree = [x for p in parts for x in p[2]]
     etree = np.asarray(etree) if etree else e
     egt[:, 2] = np.arctan2(np.sin(egt[:, 2]), np.cos(egt[:, 2]))
     # per logged pose: inside the north-star tolerance?  (with the reference order every pose is expected
@@ -320,7 +451,7 @@ def pose_check(cfg, S, gpu_poses, streams, thresholds=(-1.0, -1.0), order=0):
     if bad.size:
         i0 = int(bad[0])
         first = {"stream": int(streams[i0 // n_scans]), "scan": int(i0 % n_scans)}
-    return {"streams": len(streams), "stream_ids": (f"every 64th of {S.points.shape[0]} and the last"
+    return {"streams": len(streams), "stream_ids": (f"every 64th of {num_streams} and the last"
                                                     if len(streams) > 2 else list(streams)),
             "scans_per_stream": n_scans,
             "rmse_xy_m": float(np.sqrt(np.mean(e[:, 0] ** 2 + e[:, 1] ** 2))),
@@ -475,9 +606,9 @@ def run_gmapping(args, world, rank, dev):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    neff = 0.0
+    last_w, neff = d_w, 0.0
     for t in range(W, T):
-        _, neff = step(t)
+        last_w, neff = step(t)
     torch.cuda.synchronize()
     if neff is None:
         sums = d_sums.cpu().numpy()
@@ -488,6 +619,9 @@ def run_gmapping(args, world, rank, dev):
     fleet.set_timing(False)
     kms, kn = fleet.kernel_times(reset=True)
     s, h, f = fleet.scores()
+    if args.dump_outputs:  # the last step's scores and hit / free counts per particle, and its normalised weights
+        dump_outputs(args.dump_outputs, {"scores": s, "hits": h, "free_updates": f, "weights": last_w.cpu().numpy()},
+                     rank, world)
     t_max, total = aggregate_over_ranks(elapsed, float(P * K), dev)
     value = total / t_max
     if rank == 0:
@@ -509,7 +643,7 @@ def run_gmapping(args, world, rank, dev):
                              "counted_gbs": round(tb / avg_s / 1e9, 1),
                              "counted_frac": round(tb / avg_s / 1e9 / HBM_PEAK_GBS, 5)})
         cpu = None
-        if not args.no_cpu_baseline:  # every GPU count, rank 0 only, after the timed region
+        if args.full and not args.no_cpu_baseline:  # every GPU count, rank 0 only, after the timed region
             cpu = gmapping_cpu_baseline()
         out = {"metric": GM_METRIC, "value": round(value, 1), "unit": "particle-scans/s", "n_gpus": world, "steps": K,
                "warmup": W, "ms_per_step": round(t_max / K * 1e3, 4), "higher_is_better": True, "scaling": "strong",
@@ -600,9 +734,13 @@ def run_plicp(args, world, rank, dev):
     elapsed = time.perf_counter() - t0
     pl.set_timing(False)
     kms, kn = pl.kernel_times(reset=True)
+    if args.dump_outputs:  # the last step's sm_icp result of every pair: x[3], error, then valid / iterations / nvalid
+        raw = np.ascontiguousarray(d_out.cpu().numpy())
+        dump_outputs(args.dump_outputs, {"x_error": raw.view(np.float64)[:, :4].copy(),
+                                         "valid_iterations_nvalid": raw.view(np.int32)[:, 8:11].copy()}, rank, world)
     t_max, total = aggregate_over_ranks(elapsed, float(B * K), dev)
     if rank == 0:
-        cpu = None if args.no_cpu_baseline else plicp_cpu_baseline()
+        cpu = plicp_cpu_baseline() if args.full and not args.no_cpu_baseline else None
         out = {"metric": PL_METRIC, "value": round(total / t_max, 1), "unit": "scan-pairs/s", "n_gpus": world,
                "steps": K, "warmup": W, "ms_per_step": round(t_max / K * 1e3, 4), "higher_is_better": True,
                "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -729,11 +867,13 @@ def run_karto(args, world, rank, dev):
     sm.set_timing(False)
     kt = sm.kernel_times(reset=True)
     res = karto.results_from_bytes(d_res.cpu().numpy())
+    if args.dump_outputs:  # the last step's MatchScan result of every match
+        dump_outputs(args.dump_outputs, {k: res[k] for k in ("mean", "covariance", "response", "status")}, rank, world)
     t_max, total = aggregate_over_ranks(elapsed, float(M * K), dev)
     if shard:
         total = float(M * K)  # the same matches on every rank: the job's matches, not the ranks' sum
     if rank == 0:
-        cpu = None if args.no_cpu_baseline else karto_cpu_baseline(cfg)
+        cpu = karto_cpu_baseline(cfg) if args.full and not args.no_cpu_baseline else None
         info = sm.info
         coarse_ms, coarse_n = kt.get("kt_coarse_kernel", (0.0, 0))
         nA = 21
@@ -865,6 +1005,13 @@ def main():
     ap.add_argument("--input", choices=["ranges", "points"], default="ranges",
                     help="hector: raw LaserScan ranges through the on-device ingest (scanCallback, default) or "
                          "pre-converted DataContainer points")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the instrumented pass and its "
+                         "roofline, the copy-bandwidth probe, the CPU baselines, the pose check against the oracle and "
+                         "the targets block (a plain run sets up, warms up, times --steps steps and prints its line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB; the same inputs and sample in every run)")
     ap.add_argument("--launcher-selftest", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
 
@@ -913,18 +1060,26 @@ def main():
     B = args.streams or cfg["streams"]
     K, W = args.steps, args.warmup
     # the headline pass (K steps) runs without per-kernel events (they add ~15 us of gaps per step on
-    # MI355X); the kernel durations for the roofline come from a second, instrumented pass of K more steps
-    P = 0 if args.no_timing else K
+    # MI355X); with --full the kernel durations for the roofline come from a second, instrumented pass of K more
+    # steps on the next K scans (the first K + W scans are the same with and without it)
+    P = K if args.full and not args.no_timing else 0
     T = K + W + P
 
     # ---- synthetic input, resident in HBM before timing: [step][stream][1081][2] ----
     t0 = time.perf_counter()
-    S = synth.make_streams(B, T, seed=12345 + rank * B)
     from_ranges = args.input == "ranges"
-    if from_ranges:  # LaserScan ranges [step][stream][1081] float32
-        rng_in = np.ascontiguousarray(S.ranges.transpose(1, 0, 2))
-        d_rng = torch.from_numpy(rng_in).to(dev)
+    seed = 12345 + rank * B
+    S, log_rng, log_gt = None, [], []
+    if from_ranges:
+        # LaserScan ranges [step][stream][1081] float32, generated on the device (fill_device_ranges: set-up time
+        # does not grow with the host's work per scan).  The buffer holds the K + W scans of the warm-up and the
+        # timed steps; --full refills it with the next P scans for the instrumented pass
+        nb = synth.N_BEAMS
+        d_rng = torch.empty((K + W, B, nb), dtype=torch.float32, device=dev)
+        gt0 = fill_device_ranges(d_rng, 0, seed)
+        torch.cuda.synchronize()
     else:
+        S = synth.make_streams(B, T, seed=seed)
         pts = np.ascontiguousarray(S.points.transpose(1, 0, 2, 3))
         cnt = np.ascontiguousarray(S.counts.T.astype(np.int32))
         d_pts = torch.from_numpy(pts).to(dev)
@@ -957,9 +1112,8 @@ def main():
     fleet.set_pose_log_slots(d_plog.data_ptr(), d_slot.data_ptr(), len(log_streams), T)
     if from_ranges:
         # the node's filters with the generator's own beam directions as the unit-vector cache, so the
-        # device DataContainers equal synth's points (the pose check below replays those)
+        # device DataContainers equal synth.ranges_to_points of the same ranges (the pose check replays those)
         from slam2d.hector import HsLaser
-        nb = S.ranges.shape[2]
         ang = synth.beam_angles(nb)
         fleet.set_laser(HsLaser.defaults(nb, float(ang[0]), float(ang[1] - ang[0])),
                         unit_vectors=np.stack([np.cos(ang), np.sin(ang)], 1))
@@ -1001,21 +1155,42 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     ctr = fleet.counters(reset=True)
+    if args.dump_outputs:
+        # what the last timed step left its caller: every stream's pose, covariance, map-update flag and updated
+        # cell count (hs_get_poses), and the log-odds of every level of the first and the last stream (hs_get_map)
+        p_, cv_, did_, cells_ = fleet.poses()
+        outs = {"pose": p_, "covariance": cv_, "map_updated": did_.astype(np.float32), "updated_cells": cells_}
+        for s_ in sorted({0, B - 1}):
+            for lvl in range(cfg["levels"]):
+                outs[f"logodds_stream{s_}_level{lvl}"] = fleet.get_map(s_, lvl, want_occ=False)["logodds"]
+        dumped = dump_outputs(args.dump_outputs, outs, rank, world)
+        log(f"[bench] rank {rank}: wrote {len(dumped)} arrays to {args.dump_outputs} "
+            f"(sampled: {[n for n, i in dumped.items() if i['sampled']] or 'none'})")
 
     # instrumented pass: the same K-step workload on the next K scans, HIP events around every kernel
     # on the stream it is launched on (the library's timing events)
     ktimes, ctr_i, elapsed_i = None, None, None
     clk = None
+    if args.full and from_ranges:  # the logged streams' ranges and ground truth, for the pose check
+        d_logidx = torch.tensor(log_streams, device=dev)
+        log_rng.append(d_rng.index_select(1, d_logidx).cpu().numpy())
+        log_gt.append(gt0)
     if P:
+        if from_ranges:  # the next P scans of every stream, into the same buffer
+            gt1 = fill_device_ranges(d_rng[:P], K + W, seed)
+            log_rng.append(d_rng[:P].index_select(1, d_logidx).cpu().numpy())
+            log_gt.append(gt1)
+            torch.cuda.synchronize()
+        i0 = 0 if from_ranges else W + K   # where the instrumented pass's scans begin in the input buffer
         fleet.set_timing(True)
         fleet.set_clock_probe(True)   # effective shader clock of the instrumented pass (s_memtime / s_memrealtime)
         fleet.clock_probe(reset=True)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         if pipelined:
-            run(W + K, P)
+            run(i0, P)
         else:
-            for t in range(W + K, T):
+            for t in range(i0, i0 + P):
                 step(t)
         torch.cuda.synchronize()
         elapsed_i = time.perf_counter() - t1
@@ -1111,7 +1286,15 @@ def main():
             if not args.no_copy_probe:
                 roof["attainable_copy_GBps"] = round(copy_bandwidth(dev), 1)
         cpu = hector_cpu_block(args, cfg, thr)
-        pose = pose_check(cfg, S, d_plog.cpu().numpy(), log_streams, thresholds=thr, order=order)
+        pose = None
+        if args.full and from_ranges:
+            n_paths = log_gt[0].shape[0]
+            pose = pose_check(cfg, None, d_plog.cpu().numpy(), log_streams, thresholds=thr, order=order,
+                              log_ranges=np.concatenate(log_rng).transpose(1, 0, 2),
+                              log_gt=np.concatenate(log_gt, axis=1)[[s_ % n_paths for s_ in log_streams]],
+                              num_streams=B)
+        elif args.full:
+            pose = pose_check(cfg, S, d_plog.cpu().numpy(), log_streams, thresholds=thr, order=order)
         out = {"metric": METRIC, "value": round(value, 1), "unit": "scans/s", "n_gpus": world, "steps": K,
                "warmup": W, "ms_per_step": round(t_max / K * 1e3, 4), "higher_is_better": True,
                "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -1133,10 +1316,11 @@ def main():
                           "kernel_src_matches_tree": lib_src == tree_src,
                           "issue_split": workload["issue_split"],
                           "map_updates_per_scan": round(ctr["updates"] / max(B * K, 1), 4)},
-               "roofline": roof, "cpu_baseline": cpu, "pose_vs_ref": pose}
+               "full": args.full, "roofline": roof, "cpu_baseline": cpu, "pose_vs_ref": pose}
         if cpu:
             out["speedup_vs_cpu_1core"] = round(value / cpu["value"], 1)
-        out["targets"] = north_star_targets(value, cpu, roof, pose)
+        if args.full:
+            out["targets"] = north_star_targets(value, cpu, roof, pose)
         print(json.dumps(out), flush=True)
     fleet.close()
     if world > 1:

@@ -239,6 +239,66 @@ def test_rccl_unique_id_with_nul_bytes_gloo_world2():
     assert C.sizeof(_UniqueId) == 128
 
 
+# ------------------------------------------------------------------ bench.py --dump-outputs
+def test_dump_outputs_dtypes_budget_and_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 stays float32, integer arrays become float64 exactly, the files stay inside the
+    budget, an array over its share is cut to the same seeded cells in every call, and a multi-GPU rank writes
+    files of its own."""
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4000)
+    big = np.arange(5000, dtype=np.float32).reshape(50, 100) * 0.5
+    arrays = {"pose": np.arange(6, dtype=np.float32).reshape(2, 3), "cells": np.array([2 ** 40 + 1, -3], np.int64),
+              "map": big}
+    info = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    info_b = bench.dump_outputs(str(tmp_path / "b"), {"map": big * 2.0, "pose": arrays["pose"], "cells": arrays["cells"]})
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in arrays}
+    b = {n: np.load(tmp_path / "b" / f"{n}.npy") for n in arrays}
+    assert a["pose"].dtype == np.float32 and np.array_equal(a["pose"], arrays["pose"]) and not info["pose"]["sampled"]
+    assert a["cells"].dtype == np.float64 and a["cells"].tolist() == [2.0 ** 40 + 1, -3.0]
+    assert sum(v.nbytes for v in a.values()) <= 4000
+    assert info["map"]["sampled"] and info_b["map"]["sampled"] and a["map"].dtype == np.float32
+    assert a["map"].shape == b["map"].shape == (990,)      # (4000 - 24 - 16) // 4 cells
+    assert np.array_equal(b["map"], a["map"] * 2.0)        # the same cells, in the same order
+    assert np.all(np.diff(a["map"]) > 0) and np.isin(a["map"], big).all()
+    bench.dump_outputs(str(tmp_path / "a"), {"pose": arrays["pose"]}, rank=1, world=2)
+    assert np.array_equal(np.load(tmp_path / "a" / "pose_rank1.npy"), arrays["pose"])
+
+
+def test_device_scan_generator_matches_synth_and_depends_on_seed_and_step_alone():
+    """bench.py's scan generator (torch, here on the CPU device): its noise-free ranges are synth.cast_ranges' (the
+    same float64 intersection, so equal to rounding: 1e-9 m, and the same beams out of range but for a ray that
+    grazes a segment end), a step's scans depend on (seed, step) alone, and streams on one path differ in noise."""
+    import torch
+
+    cpu = torch.device("cpu")
+    poses, rel = bench.stream_paths(70, 0, 6)
+    assert poses.shape == (64, 6, 3) and np.array_equal(rel[:, 0], np.zeros((64, 3)))
+    want = synth.cast_ranges(poses[:3].reshape(-1, 3), synth.world_segments())
+    got = bench.cast_ranges_device(poses[:3].reshape(-1, 3), cpu, chunk=4).numpy()
+    both = np.isfinite(want) & np.isfinite(got)
+    assert (np.isfinite(want) != np.isfinite(got)).mean() <= 1e-3 and both.mean() > 0.5
+    assert np.abs(want[both] - got[both]).max() <= 1e-9
+    a = torch.empty((6, 70, synth.N_BEAMS), dtype=torch.float32)
+    b = torch.empty((2, 70, synth.N_BEAMS), dtype=torch.float32)
+    gt = bench.fill_device_ranges(a, 0, 7)
+    gt_b = bench.fill_device_ranges(b, 4, 7)
+    assert torch.equal(a[4:], b) and np.array_equal(gt[:, 4:], gt_b)            # steps 4, 5 again: the same scans
+    assert not torch.equal(a[0], a[1]) and not torch.equal(a[:, 0], a[:, 64])   # one path, two noise draws
+    d = (a[:, 0] - a[:, 64])[torch.isfinite(a[:, 0])]
+    assert 0.012 < float(d.std()) < 0.016                                       # sqrt(2) x 0.01 m
+    bench.fill_device_ranges(b, 4, 8)
+    assert not torch.equal(a[4:], b)
+    fin = torch.isfinite(a[0, 5])
+    assert np.abs(a[0, 5][fin].numpy() - synth.cast_ranges(poses[5, :1], synth.world_segments())[0][fin.numpy()]).max() < 0.06
+
+
+def test_plain_run_skips_the_cpu_block():
+    """Without --full the line's CPU block is not measured at all (hector_cpu_block), whatever --cpu-cores says."""
+    import argparse
+
+    a = argparse.Namespace(full=False, no_cpu_baseline=False, cpu_cores=2)
+    assert bench.hector_cpu_block(a, bench.CONFIGS["c2"], (-1.0, -1.0)) is None
+
+
 # ------------------------------------------------------------------ bench.py --gpus N launcher
 def _bench_env():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR",
@@ -254,7 +314,7 @@ def test_bench_gpus_n_launches_its_ranks():
     import sys
 
     r = subprocess.run([sys.executable, os.path.join(bench.REPO, "bench.py"), "--gpus", "2", "--streams", "512",
-                        "--cpu-cores", "2", "--launcher-selftest"], capture_output=True, text=True, timeout=300,
+                        "--cpu-cores", "2", "--full", "--launcher-selftest"], capture_output=True, text=True, timeout=300,
                        env=_bench_env())
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -9,6 +9,8 @@ mkdir -p "$ROOT/gpurun_out"
 # rounds alternate the order (A B, B A, ...): a lease's clock drifts over a session (the second library of a
 # pair ran 20-40 MHz lower in round 5's A/Bs), so a fixed order biases against the later variants
 SPECS=("$@")
+# --full: the summary line below prints the instrumented pass's per-kernel times and clocks
+BENCH_ARGS="--full $BENCH_ARGS"
 for round in $(seq 1 "${AB_ROUNDS:-2}"); do
   ORDER=("${SPECS[@]}")
   if [ $((round % 2)) -eq 0 ]; then ORDER=(); for ((k=${#SPECS[@]}-1; k>=0; k--)); do ORDER+=("${SPECS[$k]}"); done; fi

@@ -2,7 +2,7 @@
 # One GPU session, steps chosen by name, results under gpurun_out/<tag>/ (each step under its own limit,
 # the session stops at the first failure):
 #   tools/gpu_session.sh <tag> <step>...
-#   cold     the driver's exact bench command (python3 bench.py --gpus 1 --steps 20 --warmup 5) -> cold.json
+#   cold     the driver's bench command with --full (python3 bench.py --gpus 1 --steps 20 --warmup 5 --full) -> cold.json
 #            (run it FIRST to time a cold box: no GPU process before it)
 #   pytest   python -m pytest tests -m gpu                                                        -> pytest.log
 #   pytestab:<lib>[:<files>]  the GPU tests against lib/ab/libslam2d_<lib>.so                    -> pytest_<lib>.log
@@ -10,7 +10,7 @@
 #   mclk     tools/clk_match.py on lib/ab/libslam2d_mclk.so (the match's GN-step phase split)          -> mclk.txt
 #   smoke    __graft_entry__.smoke()                                                              -> smoke.log
 #   warm     the driver's bench command again                                                     -> warm.json
-#   bench:<name>:<args>   bench.py <args> (commas become spaces)                                   -> <name>.json
+#   bench:<name>:<args>   bench.py <args> (commas become spaces; --full for roofline and pose check) -> <name>.json
 #   ab:<lib>,<lib>...     tools/ab_bench.sh over lib/ab/libslam2d_<lib>.so ("main" = the product library)
 #   pmc:<lib>,<lib>...    tools/pmc_ab.sh counter passes per variant (PMC_SETS="set;set" to choose) -> pmc.txt
 #   prof:<name>:<args>    tools/profile_gpu.sh <tag>_<name> <args>
@@ -23,7 +23,7 @@ cd "$R"
 for step in "$@"; do
   case "$step" in
     cold|warm)
-      timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$O/$step.json" 2> "$O/$step.err" \
+      timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$O/$step.json" 2> "$O/$step.err" \
         || { echo "FAIL $step"; tail -20 "$O/$step.err"; exit 1; }
       python3 tools/ab_summary.py --line "$O/$step.json" ;;
     pytest)
