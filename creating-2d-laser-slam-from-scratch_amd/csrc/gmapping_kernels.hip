@@ -54,26 +54,7 @@ __device__ __forceinline__ void gm_lds_barrier()
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-#ifndef GM_BALLOT
-#define GM_BALLOT 1  // fan groups culled per tile by one ballot (lane f tests group f); 0: a scalar box test per group
-#endif
-#ifndef GM_RESTORE
-#define GM_RESTORE 1  // the count array is zeroed by the threads that store it (no clear + barrier per tile); 0: A/B
-#endif
-#ifndef GM_BWD
-#define GM_BWD 1  // odd lanes walk their steps backwards (neighbouring beams at different radii: fewer lanes per LDS word)
-#endif
-#ifndef GM_FAN
-#define GM_FAN 1  // lane l of a fan group rasters beam 2 (l % 32) + l / 32: each 32-lane half spans the fan (0: A/B)
-#endif
-#ifndef GM_PACKED
-#define GM_PACKED 1  // the walk's error term and LDS address packed in one register, eight steps per trip (0: A/B)
-#endif
-#ifndef GM_PRICE
-#define GM_PRICE 0  // timing-only pricing builds (wrong maps): 1 no acc pass, 2 no count stores (invalid with
-                    // GM_RESTORE: the counts then pile up), 3 no walk steps
-#endif
-// 32-bit LDS byte address of an LDS pointer, and back (GM_PACKED carries addresses in packed registers)
+// 32-bit LDS byte address of an LDS pointer, and back (the walk carries addresses in packed registers)
 typedef __attribute__((address_space(3))) unsigned gm_lds_u32;
 __device__ __forceinline__ unsigned gm_lds_addr(unsigned *p) { return (unsigned)(size_t)(gm_lds_u32 *)p; }
 __device__ __forceinline__ unsigned *gm_lds_ptr(unsigned a) { return (unsigned *)(gm_lds_u32 *)(size_t)a; }
@@ -311,11 +292,12 @@ gm_compute_kernel(GmGeom g, const double *__restrict__ poses, int n, const unsig
         }
         if ((tid & 63) == 0) gbox[b0 >> 6] = make_int4(gx0, gy0, gx1, gy1);
     }
-    // first_hit starts empty once: afterwards each hit cell's first beam restores its word in the acc pass; with
-    // GM_RESTORE the counts likewise (the store pass zeroes what it stored), and both tile flags start clear
+    // first_hit starts empty once: afterwards each hit cell's first beam restores its word in the acc pass; the
+    // counts likewise (the store pass zeroes what it stored: no clear + barrier per tile), and both tile flags
+    // start clear
     for (int k = tid; k < GM_LDS_WORDS / 4; k += GM_THREADS) {
         reinterpret_cast<uint4 *>(first_hit)[k] = make_uint4(~0u, ~0u, ~0u, ~0u);
-        if (GM_RESTORE) reinterpret_cast<uint4 *>(cnt)[k] = make_uint4(0u, 0u, 0u, 0u);
+        reinterpret_cast<uint4 *>(cnt)[k] = make_uint4(0u, 0u, 0u, 0u);
     }
     if (tid < 2) s_anyf[tid] = s_anyh[tid] = 0;
     // the written tile box: the rays' box clamped to the map
@@ -340,12 +322,7 @@ gm_compute_kernel(GmGeom g, const double *__restrict__ poses, int n, const unsig
         const int tx = tx0 + t % ntx, ty = ty0 + t / ntx;
         const int X0 = tx * GM_TILE, Y0 = ty * GM_TILE_H;
         const int X1 = min(X0 + GM_TILE, g.sx), Y1 = min(Y0 + GM_TILE_H, g.sy);
-        if (!GM_RESTORE) {
-            for (int k = tid; k < GM_LDS_WORDS / 4; k += GM_THREADS)
-                reinterpret_cast<uint4 *>(cnt)[k] = make_uint4(0u, 0u, 0u, 0u);
-            // the flag of this parity was last read two tiles ago, with barriers in between
-            if (tid == 0) s_anyf[it & 1] = s_anyh[it & 1] = 0;
-        } else if (tid == 0) {
+        if (tid == 0) {
             // the OTHER parity's flags, for the next tile: the previous tile read them after its raster barrier and
             // before its closing one (a tile without marks read s_anyf == 0, which this rewrites unchanged); this
             // tile's raster barrier orders the reset before the next tile's raster sets them
@@ -353,18 +330,18 @@ gm_compute_kernel(GmGeom g, const double *__restrict__ poses, int n, const unsig
         }
         // the fan groups (64 beams) whose box meets the tile: one ballot, lane f testing group f (groups past the
         // first 64, scans of > 4096 beams, test their box alone); this wave's groups are f = wave + 4 k
-        unsigned long long fm = 0ull;
-        if (GM_BALLOT) {
+        unsigned long long fm;
+        {
             int ol = tid & 63;  // opaque: the box address is not hoisted into a VGPR held across tiles
             asm volatile("" : "+v"(ol));
             const int4 gb = gbox[min(ol, ngr - 1)];
             fm = __ballot((int)(ol < ngr) & (int)(gb.z >= X0) & (int)(gb.x < X1) & (int)(gb.w >= Y0) & (int)(gb.y < Y1));
         }
-        if (!GM_RESTORE) gm_lds_barrier();  // the cleared counts (GM_RESTORE: the previous tile's closing barrier)
         // one fan group's raster in the tile (a lambda: the ballot's groups and the scalar-tested groups past the
         // first 64 share it)
         auto raster_group = [&](int b0) {
-            const int b = b0 + (GM_FAN ? 2 * (tid & 31) + ((tid >> 5) & 1) : (tid & 63));
+            // lane l rasters beam 2 (l % 32) + l / 32 of its group: each 32-lane half spans the fan
+            const int b = b0 + 2 * (tid & 31) + ((tid >> 5) & 1);
             if (b >= n) return;
             const unsigned r = rays[b];
             if (r == GM_RAY_INVALID) return;
@@ -381,10 +358,10 @@ gm_compute_kernel(GmGeom g, const double *__restrict__ poses, int n, const unsig
             const bool in = l.x_major ? gm_clip(l, X0, X1, Y0, Y1, lo, hi) : gm_clip(l, Y0, Y1, X0, X1, lo, hi);
             if (!in) return;
             const unsigned two_da = 2u * (unsigned)l.da, two_db = 2u * (unsigned)l.db;
-            // GM_BWD: odd lanes start at hi and walk down to lo (the same cells): near the scan origin the lanes of
+            // odd lanes start at hi and walk down to lo (the same cells): near the scan origin the lanes of
             // a fan then sit at two radii per instruction, so half as many of them add to one LDS word (the
             // atomics to one address serialise)
-            const bool bwd = GM_BWD && (tid & 1);
+            const bool bwd = tid & 1;
             const int s0 = bwd ? hi : lo;
             const unsigned num = two_db * (unsigned)s0 + (unsigned)l.da;
             const int q = l.da ? (int)gm_udiv(num, two_da) : 0;
@@ -399,13 +376,11 @@ gm_compute_kernel(GmGeom g, const double *__restrict__ poses, int n, const unsig
             // a subtract with borrow and two selects per step on byte offsets into the count array,
             // four steps per trip.  Backwards the same step with f = rem and the offsets negated: rem drops by
             // 2 db per step and the minor axis steps back exactly when it borrows (then + 2 da)
-            if (GM_PRICE == 3) return;
             const int tda = (int)two_da, tdb = (int)two_db;
             const int dabf = la * 4, dab2f = dabf + l.sb * lb * 4;
             const int dab = bwd ? -dabf : dabf, dab2 = bwd ? -dab2f : dab2f;
             int f = bwd ? (int)rem : tda - 1 - (int)rem;
             int i = 0;
-#if GM_PACKED
             // f and the step's LDS byte address in ONE register, V = f << 16 | address (LDS addresses < 2^16, f < 2 da
             // <= 2^15): subtracting 2 db << 16 borrows exactly when the minor axis steps, and one select + add then
             // moves both fields (the Hector update's walk); eight steps per trip
@@ -432,29 +407,10 @@ gm_compute_kernel(GmGeom g, const double *__restrict__ poses, int n, const unsig
             }
 #undef GM_WSTEP
             if (i < steps) atomicAdd(gm_lds_ptr(v & 0xFFFFu), 1u);
-#else
-            char *pc = reinterpret_cast<char *>(cnt) + li * 4;
-#define GM_WSTEP                                                                  \
-    do {                                                                          \
-        atomicAdd(reinterpret_cast<unsigned *>(pc), 1u); /* visits++ (:227-234) */ \
-        unsigned fu_;                                                             \
-        const bool c_ = __builtin_sub_overflow((unsigned)f, (unsigned)tdb, &fu_); \
-        f = (int)fu_ + (c_ ? tda : 0);                                            \
-        pc += c_ ? dab2 : dab;                                                    \
-    } while (0)
-            for (; i + 3 < steps; i += 4) {
-                GM_WSTEP; GM_WSTEP; GM_WSTEP; GM_WSTEP;
-            }
-            for (; i + 1 < steps; i += 2) {
-                GM_WSTEP; GM_WSTEP;
-            }
-#undef GM_WSTEP
-            if (i < steps) atomicAdd(reinterpret_cast<unsigned *>(pc), 1u);
-#endif
         };
         for (unsigned long long gmk = fm & (0x1111111111111111ull << (wbeam0 >> 6)); gmk; gmk &= gmk - 1ull)
             raster_group(__builtin_ctzll(gmk) << 6);
-        for (int b0 = wbeam0 + (GM_BALLOT ? 64 * 64 : 0); b0 < n; b0 += GM_THREADS) {
+        for (int b0 = wbeam0 + 64 * 64; b0 < n; b0 += GM_THREADS) {
             const int4 gb = gbox[b0 >> 6];
             const int gx0 = __builtin_amdgcn_readfirstlane(gb.x), gy0 = __builtin_amdgcn_readfirstlane(gb.y);
             const int gx1 = __builtin_amdgcn_readfirstlane(gb.z), gy1 = __builtin_amdgcn_readfirstlane(gb.w);
@@ -502,10 +458,10 @@ gm_compute_kernel(GmGeom g, const double *__restrict__ poses, int n, const unsig
             // address per particle, was most of this pass's time)
             phits[b] = hc;
         };
-        if (GM_PRICE != 1 && s_anyh[it & 1]) {  // (a tile where no beam ends has no acc pass)
+        if (s_anyh[it & 1]) {  // (a tile where no beam ends has no acc pass)
             for (unsigned long long gmk = fm & (0x1111111111111111ull << (wbeam0 >> 6)); gmk; gmk &= gmk - 1ull)
                 acc_group(__builtin_ctzll(gmk) << 6);
-            for (int b0 = wbeam0 + (GM_BALLOT ? 64 * 64 : 0); b0 < n; b0 += GM_THREADS) {
+            for (int b0 = wbeam0 + 64 * 64; b0 < n; b0 += GM_THREADS) {
                 const int4 gb = gbox[b0 >> 6];
                 const int gx0 = __builtin_amdgcn_readfirstlane(gb.x), gy0 = __builtin_amdgcn_readfirstlane(gb.y);
                 const int gx1 = __builtin_amdgcn_readfirstlane(gb.z), gy1 = __builtin_amdgcn_readfirstlane(gb.w);
@@ -513,18 +469,18 @@ gm_compute_kernel(GmGeom g, const double *__restrict__ poses, int n, const unsig
                 acc_group(b0);
             }
         }
-        // GM_RESTORE: the acc pass's count reads (n) precede the zeroing below
-        if (GM_RESTORE && s_anyh[it & 1]) gm_lds_barrier();
-        // counts: the whole tile (a fresh map: untouched cells written as zero), 16-B stores; GM_RESTORE: each
-        // quad zeroed by the thread that stored it
-        for (int qi = tid; qi < (GM_PRICE == 2 ? 0 : GM_TILE_CELLS / 4); qi += GM_THREADS) {
+        // the acc pass's count reads (n) precede the zeroing below
+        if (s_anyh[it & 1]) gm_lds_barrier();
+        // counts: the whole tile (a fresh map: untouched cells written as zero), 16-B stores; each quad zeroed by
+        // the thread that stored it
+        for (int qi = tid; qi < GM_TILE_CELLS / 4; qi += GM_THREADS) {
             const int row = qi >> 4, c4 = (qi & 15) << 2;
             uint4 *q = reinterpret_cast<uint4 *>(&cnt[row * GM_STRIDE + c4]);
             *reinterpret_cast<uint4 *>(&tp[row * GM_TILE + c4]) = *q;
-            if (GM_RESTORE) *q = make_uint4(0u, 0u, 0u, 0u);
+            *q = make_uint4(0u, 0u, 0u, 0u);
         }
         if (tid == 0) pstamp[ty * g.tiles_x + tx] = cur_step;
-        gm_lds_barrier();  // the tile's LDS counts are read (GM_RESTORE: and zeroed) before the next tile's raster
+        gm_lds_barrier();  // the tile's LDS counts are read (and zeroed) before the next tile's raster
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) nfree += __shfl_xor(nfree, off, 64);

@@ -292,6 +292,10 @@ bool upd_ring_ok(const hs_ctx *c)
     return c->upd_ring && c->max_points <= 5 * 256 && c->sx <= 16384 && c->sy <= 16384;
 }
 
+// (defined after launch_part, so that the library keeps its kernels in the order match, then update)
+int launch_update(hs_ctx *c, const FleetGeom &geom, int blocks, const float2 *xy, int xy_stride, int begin, int count,
+                  const UpdList *wl_cur, UpdList *wl_next, hipStream_t s);
+
 int launch_part(hs_ctx *c, int part, int begin, int count, const float2 *xy, int xy_stride, const int *n,
                 const float2 *origo, const float *hints, int mode, float *out_pose, float *out_cov, hipStream_t s,
                 hipEvent_t wait_before_update = nullptr, const MatchIngest *mi = nullptr)
@@ -303,7 +307,6 @@ int launch_part(hs_ctx *c, int part, int begin, int count, const float2 *xy, int
     WorkItem *wholes = c->d_wholes + (size_t)part * c->B * c->levels;
     // the single-kernel update consumes the match kernel's list of updating streams (wl[part][parity]: one
     // pair of lists per part)
-    const size_t upd_shmem = upd_shmem_bytes(c);
     const bool single = upd_single_ok(c);
     const bool use_list = single && !c->upd_parts_fixed && mode != MODE_MATCH_ONLY;
     UpdList *wl_cur = use_list ? c->wl[part][c->wl_parity[part]] : nullptr;
@@ -319,7 +322,7 @@ int launch_part(hs_ctx *c, int part, int begin, int count, const float2 *xy, int
     for (int l = 0; l < c->levels; ++l)
         big = big || (unsigned long long)c->geom.lv[l].tiles_x * c->geom.lv[l].tiles_y * TILE_BLOCK_WORDS >= (1ull << 30);
     if (c->reduce_order == 0) {
-        const bool regs = c->max_points <= (S2D_MATCH_CW ? CW_MAXN : MATCH_THREADS * MATCH_REG_PTS);
+        const bool regs = c->max_points <= CW_MAXN;
         if (big) {
             if (regs) S2D_MATCH_LAUNCH(true, true, true);
             else S2D_MATCH_LAUNCH(true, false, true);
@@ -349,22 +352,7 @@ int launch_part(hs_ctx *c, int part, int begin, int count, const float2 *xy, int
         }
         UpdList *wl_next = c->wl[part][c->wl_parity[part] ^ 1];
         c->wl_parity[part] ^= 1;
-        begin_timed(c, 2, s);
-        if (upd_ring_ok(c))
-            hipLaunchKernelGGL(hs_update_ring_kernel, dim3(blocks), dim3(RTHREADS), ring_shmem_bytes(c), s, c->geom,
-                               c->d_cells, c->d_state, xy, xy_stride, c->d_ixy, c->max_points, begin, count, c->max_points,
-                               wl_cur, wl_next, c->ncu);
-        else if (upd_rays_in_regs(c))
-            hipLaunchKernelGGL((hs_update_kernel<UPD_RREG>), dim3(blocks), dim3(UPD_THREADS), upd_shmem, s, c->geom, c->d_cells,
-                               c->d_state, xy, xy_stride, c->d_ixy, c->max_points, begin, count, c->max_points, wl_cur,
-                               wl_next, c->ncu);
-        else
-            hipLaunchKernelGGL((hs_update_kernel<0>), dim3(blocks), dim3(UPD_THREADS), upd_shmem, s, c->geom, c->d_cells,
-                               c->d_state, xy, xy_stride, c->d_ixy, c->max_points, begin, count, c->max_points, wl_cur,
-                               wl_next, c->ncu);
-        end_timed(c, s);
-        HCHK(hipGetLastError());
-        return HS_OK;
+        return launch_update(c, c->geom, blocks, xy, xy_stride, begin, count, wl_cur, wl_next, s);
     }
     if (single) {
         FleetGeom gg = c->geom;
@@ -382,24 +370,9 @@ int launch_part(hs_ctx *c, int part, int begin, int count, const float2 *xy, int
                 gg.upd_parts[l] = v < 1 ? 1 : (v > 64 ? 64 : v);
             }
         }
-        begin_timed(c, 2, s);
         int blocks = 0;
         for (int l = 0; l < c->levels; ++l) blocks += gg.upd_parts[l] * count;
-        if (upd_ring_ok(c))
-            hipLaunchKernelGGL(hs_update_ring_kernel, dim3(blocks), dim3(RTHREADS), ring_shmem_bytes(c), s, gg, c->d_cells,
-                               c->d_state, xy, xy_stride, c->d_ixy, c->max_points, begin, count, c->max_points,
-                               (const UpdList *)nullptr, (UpdList *)nullptr, c->ncu);
-        else if (upd_rays_in_regs(c))
-            hipLaunchKernelGGL((hs_update_kernel<UPD_RREG>), dim3(blocks), dim3(UPD_THREADS), upd_shmem, s, gg, c->d_cells,
-                               c->d_state, xy, xy_stride, c->d_ixy, c->max_points, begin, count, c->max_points, (const UpdList *)nullptr,
-                               (UpdList *)nullptr, c->ncu);
-        else
-            hipLaunchKernelGGL((hs_update_kernel<0>), dim3(blocks), dim3(UPD_THREADS), upd_shmem, s, gg, c->d_cells,
-                               c->d_state, xy, xy_stride, c->d_ixy, c->max_points, begin, count, c->max_points, (const UpdList *)nullptr,
-                               (UpdList *)nullptr, c->ncu);
-        end_timed(c, s);
-        HCHK(hipGetLastError());
-        return HS_OK;
+        return launch_update(c, gg, blocks, xy, xy_stride, begin, count, nullptr, nullptr, s);
     }
     begin_timed(c, 1, s);
     hipLaunchKernelGGL(hs_bin_kernel, dim3(count), dim3(BIN_THREADS), 0, s, c->geom, c->d_state, xy, xy_stride, c->d_ixy,
@@ -409,6 +382,30 @@ int launch_part(hs_ctx *c, int part, int begin, int count, const float2 *xy, int
     begin_timed(c, 2, s);
     hipLaunchKernelGGL(hs_tile_kernel, dim3(c->tile_grid), dim3(TILE_THREADS), 0, s, c->geom, c->d_cells, c->d_state,
                        c->d_rays, segs, items, wholes, wq, c->max_points);
+    end_timed(c, s);
+    HCHK(hipGetLastError());
+    return HS_OK;
+}
+
+// The single-kernel grid update of one launch_part: the ring kernel, or hs_update_kernel with the rays in
+// registers or in LDS.  wl_cur / wl_next: the match kernel's lists of updating streams (null: every stream of
+// the batch, split by geom.upd_parts).
+int launch_update(hs_ctx *c, const FleetGeom &geom, int blocks, const float2 *xy, int xy_stride, int begin, int count,
+                  const UpdList *wl_cur, UpdList *wl_next, hipStream_t s)
+{
+    begin_timed(c, 2, s);
+    if (upd_ring_ok(c))
+        hipLaunchKernelGGL(hs_update_ring_kernel, dim3(blocks), dim3(RTHREADS), ring_shmem_bytes(c), s, geom, c->d_cells,
+                           c->d_state, xy, xy_stride, c->d_ixy, c->max_points, begin, count, c->max_points, wl_cur,
+                           wl_next, c->ncu);
+    else if (upd_rays_in_regs(c))
+        hipLaunchKernelGGL((hs_update_kernel<UPD_RREG>), dim3(blocks), dim3(UPD_THREADS), upd_shmem_bytes(c), s, geom,
+                           c->d_cells, c->d_state, xy, xy_stride, c->d_ixy, c->max_points, begin, count, c->max_points,
+                           wl_cur, wl_next, c->ncu);
+    else
+        hipLaunchKernelGGL((hs_update_kernel<0>), dim3(blocks), dim3(UPD_THREADS), upd_shmem_bytes(c), s, geom,
+                           c->d_cells, c->d_state, xy, xy_stride, c->d_ixy, c->max_points, begin, count, c->max_points,
+                           wl_cur, wl_next, c->ncu);
     end_timed(c, s);
     HCHK(hipGetLastError());
     return HS_OK;

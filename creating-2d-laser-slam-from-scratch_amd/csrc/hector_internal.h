@@ -22,11 +22,8 @@ constexpr int MATCH_WAVES = MATCH_THREADS / 64;
 // E, so h never overflows 16 bits.  The grid update thus writes 2 B of index per marked cell instead of 4
 // (round 5: the 4-B index stores were a quarter of hs_update_kernel's time).
 // A tile is exactly the unit the grid-update kernel reads and writes.
-#ifndef S2D_TILE_H
-#define S2D_TILE_H 32
-#endif
 constexpr int TILE = 64;
-constexpr int TILE_H = S2D_TILE_H;
+constexpr int TILE_H = 32;
 constexpr int TILE_CELLS = TILE * TILE_H;   // 2048 at 64 x 32
 constexpr int ORD_OFF = TILE_CELLS;                    // 4-byte word offset of the 16-bit ordinal plane
 constexpr int COLD_OFF = TILE_CELLS + TILE_CELLS / 2;   // 4-byte word offset of the 32-bit index plane

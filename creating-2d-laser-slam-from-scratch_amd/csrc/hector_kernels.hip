@@ -196,16 +196,13 @@ __device__ __forceinline__ bool ingest_beam(const IngestGeom &ig, double2 u, flo
 // every thread's offset = the counts of the earlier chunks and of the lower waves of its own); longer scans
 // take the chunk loop (two barriers per chunk).
 constexpr int ING_CHUNKS = 5;  // 1280 beams
-#ifndef S2D_ING_PRELOAD
-#define S2D_ING_PRELOAD 1  // 0: the chunk loop for every scan (A/B)
-#endif
 constexpr int ING_SW = 4 * ING_CHUNKS;
 __device__ __forceinline__ int ingest_scan(const IngestGeom &ig, const double2 *__restrict__ cs,
                                            const float *__restrict__ r, float2 *__restrict__ out, float2 *stage,
                                            int *s_w)
 {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (S2D_ING_PRELOAD && ig.n <= 256 * ING_CHUNKS) {
+    if (ig.n <= 256 * ING_CHUNKS) {
         float rr[ING_CHUNKS];
         double2 uu[ING_CHUNKS];
 #pragma unroll
@@ -495,10 +492,7 @@ __device__ __forceinline__ void wave_butterfly(float (&acc)[NV])
         acc[k] = acc[k] + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc[k]), 0xB1, 0xF, 0xF, false));
 }
 
-#ifndef S2D_MATCH_BATCH
-#define S2D_MATCH_BATCH 2
-#endif
-constexpr int MATCH_BATCH = S2D_MATCH_BATCH;  // points per thread with gathers in flight together
+constexpr int MATCH_BATCH = 2;  // points per thread with gathers in flight together
 
 // One Gauss-Newton step, ScanMatcher::estimateTransformationLogLh (H/matcher/ScanMatcher.h:107-139),
 // points read from HBM (scans of more than MATCH_THREADS * MATCH_REG_PTS points).
@@ -586,7 +580,7 @@ __device__ __forceinline__ void gn_step(const float *__restrict__ cells, const L
     }
 }
 
-// gn_step with the thread's points resident in registers (n <= MATCH_THREADS * NP): every gather of
+// The tree-order gn_step with the thread's points resident in registers (n <= MATCH_THREADS * NP): every gather of
 // the step is issued before the first is consumed -- one memory round trip per Gauss-Newton step.
 // Accumulation order per thread is i = tid, tid + 256, ... as in gn_step.
 // Neighbourhood cache: the 4 cell probabilities a point computed last time (GridMapCacheArray's role,
@@ -606,12 +600,11 @@ constexpr unsigned NB_NONE = 0xFFFFFFFFu;
 // (s_pose[parity]: est[3], cos, sin, H[9], clamp flag); the other waves would only repeat it.
 constexpr int POSE_WORDS = 16;
 
-template <int NP, bool SEQ>
+template <int NP>
 __device__ __forceinline__ void gn_step_reg(const float *__restrict__ cells, const LevelGeom &g, const float2 (&p)[NP],
                                             int n, float f, float *est, float &cs, float &sn, float *H,
                                             float (*red)[MATCH_WAVES][9], int parity, unsigned *nb_key,
-                                            float4 *nb_val, unsigned short *mlist, float (*s_pose)[POSE_WORDS],
-                                            float *seqT)
+                                            float4 *nb_val, unsigned short *mlist, float (*s_pose)[POSE_WORDS])
 {
     const int tid = threadIdx.x;
     PointFetch pf[NP];
@@ -682,57 +675,34 @@ __device__ __forceinline__ void gn_step_reg(const float *__restrict__ cells, con
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     const int wave = tid >> 6;
-    const int cw = chain_wave();  // the chain / step-tail wave
-    float run = 0.0f;                                       // SEQ: lane k < 9 of wave cw: sum of term k
-    if constexpr (SEQ) {
-        // chunk j = points j * 256 .. j * 256 + 255 = slot j of every thread, in point order
+    const int cw = chain_wave();  // the step-tail wave
+    float acc[9];
 #pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            if (j * MATCH_THREADS >= n) break;  // uniform
-            const int slot = tid + j * MATCH_THREADS;
-            float t[9];
-            if (slot < n) {
-                if (pf[j].in) {
-                    const float4 v = nb_val[slot];
-                    pf[j].l[0] = v.x; pf[j].l[1] = v.y; pf[j].l[2] = v.z; pf[j].l[3] = v.w;
-                }
-                point_terms<true>(pf[j], cs, sn, t);
-            }
-            seq_chunk(seqT, t, slot < n, j == 0, min(MATCH_THREADS, n - j * MATCH_THREADS), cw, run);
+    for (int k = 0; k < 9; ++k) acc[k] = 0.0f;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const int slot = tid + j * MATCH_THREADS;
+        if (slot >= n) continue;
+        if (pf[j].in) {
+            const float4 v = nb_val[slot];
+            pf[j].l[0] = v.x; pf[j].l[1] = v.y; pf[j].l[2] = v.z; pf[j].l[3] = v.w;
         }
-    } else {
-        float acc[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) acc[k] = 0.0f;
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            const int slot = tid + j * MATCH_THREADS;
-            if (slot >= n) continue;
-            if (pf[j].in) {
-                const float4 v = nb_val[slot];
-                pf[j].l[0] = v.x; pf[j].l[1] = v.y; pf[j].l[2] = v.z; pf[j].l[3] = v.w;
-            }
-            point_accum<true>(pf[j], cs, sn, acc);
-        }
-        wave_butterfly(acc);  // 64-lane xor butterfly, offsets 32..1
-        if ((tid & 63) == 0) {
-#pragma unroll
-            for (int k = 0; k < 9; ++k) red[parity][wave][k] = acc[k];
-        }
-        __syncthreads();
+        point_accum<true>(pf[j], cs, sn, acc);
     }
+    wave_butterfly(acc);  // 64-lane xor butterfly, offsets 32..1
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) red[parity][wave][k] = acc[k];
+    }
+    __syncthreads();
     float *sp = s_pose[parity];
     if (wave == cw) {
         float s[9];
-        if constexpr (SEQ) {
-            seq_gather(run, s);
-        } else {
 #pragma unroll
-            for (int k = 0; k < 9; ++k) {
-                float a0 = red[parity][0][k] + red[parity][2][k];
-                float a1 = red[parity][1][k] + red[parity][3][k];
-                s[k] = a0 + a1;
-            }
+        for (int k = 0; k < 9; ++k) {
+            float a0 = red[parity][0][k] + red[parity][2][k];
+            float a1 = red[parity][1][k] + red[parity][3][k];
+            s[k] = a0 + a1;
         }
         float b[3] = {s[0], s[1], s[2]};
         H[0] = s[3]; H[4] = s[4]; H[8] = s[5];
@@ -780,42 +750,26 @@ __device__ __forceinline__ void gn_step_reg(const float *__restrict__ cells, con
 // chunk cost the chain (256 dependent adds) plus that wave's share of the next chunk's terms, and the
 // other waves waited for it at every hand-off (chunk loop 15.4 k of a GN step's 24 k cycles).  Here the
 // chain wave cw holds no points: the other three waves own the scan (point i = chunk * CW_PTS + pt, pt the
-// thread's rank among the 192 point threads, CW_NP slots each: scans of <= 1152 points) and fill two
-// alternating term buffers, one barrier per chunk -- at barrier j the point waves have stored chunk j and
-// the chain wave has finished chunk j - 1, whose buffer the point waves fill next.  The chain wave goes from
-// chunk to chunk without waiting for terms.  The adds are the same chain in the same order as
+// thread's rank among the 192 point threads, CW_NP slots each: scans of <= 1152 points) and fill one term
+// buffer, two barriers per chunk -- the first when the chain wave has finished chunk j - 1, the second when
+// the point waves have stored chunk j.  The adds are the same chain in the same order as
 // getCompleteHessianDerivs (OccGridMapUtil.h:94-126), so H / b are bit-identical to round 3's.
 constexpr int CW_PTS = MATCH_THREADS - 64;        // point threads
 constexpr int CW_NP = 6;                           // slots per point thread
 constexpr int CW_MAXN = CW_PTS * CW_NP;            // 1152 points in registers
 constexpr int CW_STRIDE = CW_PTS + 4;              // term-buffer row (words): 16-B aligned, row k on bank 4k
 constexpr int CW_BUF = 9 * CW_STRIDE;              // one chunk's terms
-// term buffers: 1 (default: two barriers per chunk; 31.3 KB of LDS with REGS, 5 workgroups per CU) or 2 (one
-// barrier per chunk; 38.3 KB, 4 workgroups per CU).  Measured (profiles/r04/ab_r04d*): match 0.340 / 0.345 ms at
-// 2048 streams; at 2560 streams (two whole rounds at 5 per CU) the one-buffer match is 0.395 ms, 1.56 M scans/s
-#ifndef S2D_CW_BUFS
-#define S2D_CW_BUFS 1
-#endif
-constexpr int CW_BUFS = S2D_CW_BUFS;
-#ifndef S2D_MATCH_CW
-#define S2D_MATCH_CW 1  // 0: round 3's chain wave that also computes terms (A/B builds)
-#endif
-// 1 (default; one term buffer only): the moved points' probability conversions are shared by all four waves --
-// the idle chain wave too -- over the three point waves' miss lists, between two barriers, instead of each point
-// wave converting its own list (the longest list set the start of chunk 0).  0: per-wave lists (A/B).
-#ifndef S2D_CW_SHARECONV
-#define S2D_CW_SHARECONV 1
-#endif
-constexpr bool CW_SHARE = S2D_CW_SHARECONV && CW_BUFS == 1;
+// One term buffer (two barriers per chunk; 31.3 KB of LDS with REGS, 5 workgroups per CU), not two alternating
+// ones (one barrier per chunk; 38.3 KB, 4 workgroups per CU).  Measured (profiles/r04/ab_r04d*): match 0.340 /
+// 0.345 ms at 2048 streams; at 2560 streams (two whole rounds at 5 per CU) the one-buffer match is 0.395 ms,
+// 1.56 M scans/s.
+// The moved points' probability conversions are shared by all four waves -- the idle chain wave too -- over the
+// three point waves' miss lists, between two barriers, instead of each point wave converting its own list (the
+// longest list set the start of chunk 0).
 // wave priority of every wave from a Gauss-Newton step's start to chunk 0's store (the phase the chain waits
 // for: transform, gathers, conversions, chunk 0's terms), so it issues ahead of co-resident workgroups' point
-// waves working ahead on later chunks; 0 = default priority (A/B)
-#ifndef S2D_PRECHAIN_PRIO
-#define S2D_PRECHAIN_PRIO 2
-#endif
-#ifndef S2D_PROLOGUE_PRIO
-#define S2D_PROLOGUE_PRIO 1  // the kernel's prologue and every level's start at that priority too (0: A/B)
-#endif
+// waves working ahead on later chunks; the kernel's prologue and every level's start run at that priority too
+constexpr int PRECHAIN_PRIO = 2;
 
 // cell_word for a cell inside the level (x, y < 2^15) in unsigned 32-bit arithmetic: shifts, masks and one
 // 24-bit multiply (the tile index < 2^13 times the block words), no 64-bit address math.  The match's gathers
@@ -838,9 +792,9 @@ __device__ __forceinline__ void gn_step_cw(const float *__restrict__ cells, cons
     const int wave = tid >> 6;
     const int nch = (n + CW_PTS - 1) / CW_PTS;  // chunks (uniform)
     float run = 0.0f;                           // chain wave, lane k < 9: the running sum of term k
-    __shared__ int s_mcnt[4];                   // CW_SHARE: each point wave's miss count
-    unsigned short *wl0 = reinterpret_cast<unsigned short *>(seqT + (CW_BUFS - 1) * CW_BUF);  // the miss lists
-    if (S2D_PRECHAIN_PRIO) __builtin_amdgcn_s_setprio(S2D_PRECHAIN_PRIO);
+    __shared__ int s_mcnt[4];                   // each point wave's miss count
+    unsigned short *wl0 = reinterpret_cast<unsigned short *>(seqT);  // the miss lists
+    __builtin_amdgcn_s_setprio(PRECHAIN_PRIO);
     if (wave != cw) {
         // the moved points' neighbourhoods go straight from HBM into the cache planes by LDS-DMA (no VGPRs hold
         // them; the transform is recomputed for the terms below)
@@ -890,10 +844,9 @@ __device__ __forceinline__ void gn_step_cw(const float *__restrict__ cells, cons
                 __builtin_amdgcn_global_load_lds((gv *)a3, (lv *)(nbf + 3 * CW_MAXN + sb), 4, 0, 0);
             }
         }
-        // park the gathered log-odds of every miss in its slot and list the slot for this wave (the list lives
-        // in the last term buffer: with two, first written after chunk 0's barrier; with one, chunk 0 is stored
-        // after a barrier that follows every wave's conversions), then convert 64 at a time
-        unsigned short *wl = reinterpret_cast<unsigned short *>(seqT + (CW_BUFS - 1) * CW_BUF) + pw * (NP * 64);
+        // list the slot of every miss for this wave (the list lives in the term buffer: chunk 0 is stored after
+        // a barrier that follows every wave's conversions)
+        unsigned short *wl = reinterpret_cast<unsigned short *>(seqT) + pw * (NP * 64);
         int nmiss = 0;
 #pragma unroll
         for (int j = 0; j < NP; ++j) {
@@ -913,20 +866,11 @@ __device__ __forceinline__ void gn_step_cw(const float *__restrict__ cells, cons
             // a level's first step: every in-map point missed (the keys were reset); each point thread converts its
             // own slots chunk by chunk below, so chunk 0's terms -- and the chain -- start after one sixth of the
             // conversions, and chunk j + 1's overlap the chain's chunk j
-        } else if constexpr (CW_SHARE) {
-            if (lane == 0) s_mcnt[pw] = nmiss;
         } else {
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            float *nbf = reinterpret_cast<float *>(nb_val);
-            for (int e = lane; e < nmiss; e += 64) {
-                const int slot = wl[e];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) nbf[c * CW_MAXN + slot] = cell_prob(nbf[c * CW_MAXN + slot]);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            if (lane == 0) s_mcnt[pw] = nmiss;
         }
     }
-    if (CW_SHARE && !first) {
+    if (!first) {
         // every wave converts entries wave * 64 + lane + 256 k of the three lists laid end to end; the second
         // barrier also retires the lists before chunk 0's terms overwrite them
         lds_barrier();
@@ -941,7 +885,7 @@ __device__ __forceinline__ void gn_step_cw(const float *__restrict__ cells, cons
         lds_barrier();
     }
     if (wave != cw) {
-        // chunk j = slot j of every point thread, in point order; buffer j & 1
+        // chunk j = slot j of every point thread, in point order
 #pragma unroll
         for (int j = 0; j < NP; ++j) {
             if (j >= nch) break;  // uniform
@@ -973,25 +917,22 @@ __device__ __forceinline__ void gn_step_cw(const float *__restrict__ cells, cons
             }
             // (barriers only in wave-uniform control flow: a wave whose lanes straddle n runs both sides of
             // the slot test)
-            if (CW_BUFS == 1 && (!CW_SHARE || j > 0)) lds_barrier();  // the chain wave is done with chunk j - 1 (j = 0: the miss lists)
+            if (j > 0) lds_barrier();  // the chain wave is done with chunk j - 1 (j = 0: the conversions' closing barrier)
             if (slot < n) {
-                float *T = seqT + (CW_BUFS == 2 ? (j & 1) * CW_BUF : 0);
 #pragma unroll
-                for (int k = 0; k < 9; ++k) T[k * CW_STRIDE + pt] = t[k];
+                for (int k = 0; k < 9; ++k) seqT[k * CW_STRIDE + pt] = t[k];
             }
-            lds_barrier();  // chunk j stored (two buffers: and the chain wave is done with chunk j - 1)
-            if (S2D_PRECHAIN_PRIO && j == 0) __builtin_amdgcn_s_setprio(0);
+            lds_barrier();  // chunk j stored
+            if (j == 0) __builtin_amdgcn_s_setprio(0);
         }
     } else {
         // the chain: lane k < 9 extends the sum of term k over each chunk, at s_setprio 3 through the step tail
         // (the workgroup's critical path issues ahead of co-resident workgroups' waves)
         __builtin_amdgcn_s_setprio(3);
         for (int j = 0; j < nch; ++j) {
-            if (CW_BUFS == 1 && (!CW_SHARE || j > 0)) lds_barrier();
+            if (j > 0) lds_barrier();
             lds_barrier();
-            if (lane < 9)
-                run = seq_chain_t<CW_STRIDE>(seqT + (CW_BUFS == 2 ? (j & 1) * CW_BUF : 0), lane, min(CW_PTS, n - j * CW_PTS),
-                                             run);
+            if (lane < 9) run = seq_chain_t<CW_STRIDE>(seqT, lane, min(CW_PTS, n - j * CW_PTS), run);
         }
     }
     float *sp = s_pose[parity];
@@ -1045,9 +986,7 @@ constexpr int MATCH_REG_PTS = 5;  // points per thread kept in registers: scans 
 // instance needs 26.1 KB of LDS, so six workgroups share a CU (5 before: 31.3 KB, 89 VGPRs).  Measured
 // (profiles/r06/ab_r06h*, ab_r06i*): match -1.9 % at the north star, -2.9 % under the node's gate; the
 // other instances (tree order, HBM path) stay unconstrained (1)
-#ifndef S2D_MATCH_WAVES
-#define S2D_MATCH_WAVES 6
-#endif
+constexpr int MATCH_SEQ_WAVES = 6;
 // SEQ (default): H / b summed in the reference's sequential point order; else the tree order
 // (SLAM2D_MATCH_ORDER=tree / hs_set_reduction_order: faster, poses within float reassociation of the
 // reference's).
@@ -1057,7 +996,7 @@ constexpr int MATCH_REG_PTS = 5;  // points per thread kept in registers: scans 
 // BIG: some level holds 2^30 words or more (maps above ~20000^2 cells): the reference-order gathers use 64-bit
 // addresses (cell_word) instead of 32-bit byte offsets from the level base (cell_off)
 template <bool SEQ, bool REGS, bool BIG>
-__global__ void __launch_bounds__(MATCH_THREADS) __attribute__((amdgpu_waves_per_eu((SEQ && REGS) ? S2D_MATCH_WAVES : 1)))
+__global__ void __launch_bounds__(MATCH_THREADS) __attribute__((amdgpu_waves_per_eu((SEQ && REGS) ? MATCH_SEQ_WAVES : 1)))
 hs_match_kernel(FleetGeom geom, const float *__restrict__ cells, StreamState *__restrict__ state,
                 const float2 *__restrict__ xy, int xy_stride, const int *__restrict__ counts,
                 const float2 *__restrict__ origo, const float *__restrict__ hints, int stream_begin, int mode,
@@ -1066,16 +1005,15 @@ hs_match_kernel(FleetGeom geom, const float *__restrict__ cells, StreamState *__
 {
     static_assert(MATCH_THREADS == 64 * MATCH_WAVES && MATCH_WAVES == 4, "reduction tree assumes 4 waves");
     __shared__ float red[2][MATCH_WAVES][9];
-    // SEQ: two chunks' terms for the chain wave (gn_step_cw; its miss lists live in the second), or one
-    // 256-point chunk of the HBM path (gn_step); tree order: the miss lists
-    constexpr bool CW = SEQ && S2D_MATCH_CW;                          // gn_step_cw (else round 3's gn_step_reg)
-    constexpr int NPR = CW ? CW_NP : MATCH_REG_PTS;                   // point slots per thread in registers
-    constexpr int NSLOT = CW ? CW_MAXN : MATCH_REG_PTS * MATCH_THREADS;
-    constexpr int SEQ_LDS = !CW ? SEQ_WORDS : ((CW_BUFS * CW_BUF > SEQ_WORDS || REGS) ? CW_BUFS * CW_BUF : SEQ_WORDS);
+    // SEQ (gn_step_cw; else the tree order's gn_step_reg): one chunk's terms for the chain wave (its miss lists
+    // live there too), or one 256-point chunk of the HBM path (gn_step)
+    constexpr int NPR = SEQ ? CW_NP : MATCH_REG_PTS;                  // point slots per thread in registers
+    constexpr int NSLOT = SEQ ? CW_MAXN : MATCH_REG_PTS * MATCH_THREADS;
+    constexpr int SEQ_LDS = (CW_BUF > SEQ_WORDS || REGS) ? CW_BUF : SEQ_WORDS;
     __shared__ __attribute__((aligned(16))) float seqT[SEQ ? SEQ_LDS : 4];
-    __shared__ unsigned nb_key[CW ? 4 : NSLOT];  // (the chain-wave path keeps its cached keys in registers: kreg)
+    __shared__ unsigned nb_key[SEQ ? 4 : NSLOT];  // (the chain-wave path keeps its cached keys in registers: kreg)
     __shared__ float4 nb_val[NSLOT];
-    __shared__ unsigned short mlist[CW ? 4 : MATCH_REG_PTS * MATCH_THREADS];  // tree order: per wave, the slots whose cell moved
+    __shared__ unsigned short mlist[SEQ ? 4 : MATCH_REG_PTS * MATCH_THREADS];  // tree order: per wave, the slots whose cell moved
     __shared__ float s_pose[2][POSE_WORDS];                             // a step's result, by parity
     const int local = blockIdx.x;
     const int s = stream_begin + local;
@@ -1085,7 +1023,7 @@ hs_match_kernel(FleetGeom geom, const float *__restrict__ cells, StreamState *__
     // an LDS copy in nb_val's space, read into registers below before nb_val's first use
     const bool fused = mi.ranges != nullptr;
     // the prologue (ingest, pose) and every level's start are on the stream's path like a step's pre-chain phase
-    if (S2D_PRECHAIN_PRIO && S2D_PROLOGUE_PRIO) __builtin_amdgcn_s_setprio(S2D_PRECHAIN_PRIO);
+    __builtin_amdgcn_s_setprio(PRECHAIN_PRIO);
     load_exptab();
     if (!fused) __syncthreads();  // (fused: the ingest's barriers order the table before its first use)
     const float *scells = cells + (size_t)s * geom.stream_words;
@@ -1124,12 +1062,12 @@ hs_match_kernel(FleetGeom geom, const float *__restrict__ cells, StreamState *__
         // SEQ: the chain wave cw holds no points; point thread pt owns points pt + j * CW_PTS (gn_step_cw)
         const int cw = chain_wave();
         const int wv = (int)threadIdx.x >> 6;
-        const bool owner = !CW || wv != cw;
-        const int pt = CW ? ((wv < cw ? wv : wv - 1) * 64 + ((int)threadIdx.x & 63)) : (int)threadIdx.x;
-        const int pstride = CW ? CW_PTS : MATCH_THREADS;
+        const bool owner = !SEQ || wv != cw;
+        const int pt = SEQ ? ((wv < cw ? wv : wv - 1) * 64 + ((int)threadIdx.x & 63)) : (int)threadIdx.x;
+        const int pstride = SEQ ? CW_PTS : MATCH_THREADS;
         const bool in_regs = n <= pstride * NPR;
         float2 preg[NPR];
-        unsigned kreg[NPR];  // CW: each owned slot's neighbourhood-cache key (NB_NONE: nothing cached)
+        unsigned kreg[NPR];  // SEQ: each owned slot's neighbourhood-cache key (NB_NONE: nothing cached)
 #pragma unroll
         for (int j = 0; j < NPR; ++j) {
             const int i = pt + j * pstride;
@@ -1160,24 +1098,24 @@ hs_match_kernel(FleetGeom geom, const float *__restrict__ cells, StreamState *__
             const LevelGeom &g = geom.lv[lvl];
             const int iters = lvl == 0 ? 5 : 3;
             if (n == 0) continue;  // ScanMatcher::matchData returns the hint (ScanMatcher.h:65, :96)
-            if (S2D_PRECHAIN_PRIO && S2D_PROLOGUE_PRIO) __builtin_amdgcn_s_setprio(S2D_PRECHAIN_PRIO);
+            __builtin_amdgcn_s_setprio(PRECHAIN_PRIO);
             const float *lc = scells + g.word_offset;
             float est[3], H[9];
             map_from_world(g, tmp, est);
 #pragma unroll
             for (int j = 0; j < NPR; ++j) {
-                if constexpr (CW) kreg[j] = NB_NONE;
+                if constexpr (SEQ) kreg[j] = NB_NONE;
                 else if (owner) nb_key[pt + j * pstride] = NB_NONE;  // own slots
             }
             float cs = sdm_cosf(est[2]), sn = sdm_sinf(est[2]);
             for (int it = 0; it <= iters; ++it) {
                 if (in_regs) {
-                    if constexpr (CW)
+                    if constexpr (SEQ)
                         gn_step_cw<NPR, BIG>(lc, g, preg, n, g.pts_scale, est, cs, sn, parity, kreg, nb_val, s_pose, seqT,
                                              cw, pt, it == 0);
                     else
-                        gn_step_reg<NPR, SEQ>(lc, g, preg, n, g.pts_scale, est, cs, sn, H, red, parity, nb_key,
-                                              nb_val, mlist, s_pose, seqT);
+                        gn_step_reg<NPR>(lc, g, preg, n, g.pts_scale, est, cs, sn, H, red, parity, nb_key, nb_val,
+                                         mlist, s_pose);
                     clamps += s_pose[parity][14] != 0.0f ? 1 : 0;
                 } else if constexpr (!REGS) {
                     gn_step<SEQ>(lc, g, pts, n, g.pts_scale, est, H, red, parity, &clamps, seqT);
@@ -1187,7 +1125,7 @@ hs_match_kernel(FleetGeom geom, const float *__restrict__ cells, StreamState *__
             est[2] = normalize_angle(est[2]);
             // the last step's H: the chain-wave path left it in s_pose only (parity has moved past it)
 #pragma unroll
-            for (int k = 0; k < 9; ++k) cov[k] = (CW && in_regs) ? s_pose[parity ^ 1][5 + k] : H[k];
+            for (int k = 0; k < 9; ++k) cov[k] = (SEQ && in_regs) ? s_pose[parity ^ 1][5 + k] : H[k];
             cov_h = true;
             world_from_map(g, est, tmp);
         }
@@ -1282,13 +1220,8 @@ hs_match_kernel(FleetGeom geom, const float *__restrict__ cells, StreamState *__
 // Every ray starts at the common begin cell; a ray is stored as its end cell (packed y<<16 | x) or
 // RAY_INVALID when updateByScan would skip it (begin == end :157, or begin/end outside :226-238).
 constexpr unsigned RAY_INVALID = 0xFFFFFFFFu;
-// waves per hs_update_kernel workgroup: 4 (default: 256 threads, 64 x 32-cell LDS tiles, 8 workgroups per CU) or 8
-// (512 threads, 64 x 64-cell tiles, 4 per CU: the same 32 waves per CU, half the tile visits and clip setups)
-#ifndef S2D_UPD_WAVES
-#define S2D_UPD_WAVES 4
-#endif
-constexpr int UPD_WAVES = S2D_UPD_WAVES;
-static_assert(UPD_WAVES == 4 || UPD_WAVES == 8, "hs_update_kernel: 4 or 8 waves per workgroup");
+// waves per hs_update_kernel workgroup: 256 threads, 64 x 32-cell LDS tiles, 8 workgroups per CU
+constexpr int UPD_WAVES = 4;
 constexpr int UPD_THREADS = 64 * UPD_WAVES;
 // two LDS words per tile cell, both updated with blind atomicMin (no read-modify-write chain):
 //   first_hit[c]  = smallest beam whose end cell is c      (NONE if none)
@@ -1349,9 +1282,6 @@ __device__ __forceinline__ unsigned make_ray(const LevelGeom &g, const RayFrame 
 //   step i in [0, da]:  a(i) = a0 + sa*i,  b(i) = b0 + sb*q(i),  q(i) = floor((e0 + i*db) / da),
 // e0 = da/2 (error_b start, :254/:260).  The incremental error walk keeps error in [0, da), so this
 // is exactly the cell sequence of the reference; steps 0..da-1 are freed, step da is the end cell.
-#ifndef S2D_FAST_UDIV
-#define S2D_FAST_UDIV 1
-#endif
 // n / d for n < 2^31, 1 <= d < 2^16: a float reciprocal estimate (relative error < 2^-22) and one
 // correction step each way -- ~8 instructions instead of the ~25 of the integer division sequence.
 // Exact whenever the quotient is < 2^16, which covers every step index (<= 32767) it is compared
@@ -1372,7 +1302,6 @@ __device__ __forceinline__ unsigned udiv_rcp(unsigned n, unsigned d, float rcp_d
 }
 __device__ __forceinline__ unsigned udiv_small(unsigned n, unsigned d, unsigned &rem)  // quotient and remainder
 {
-#if S2D_FAST_UDIV
     unsigned q = (unsigned)((float)n * __builtin_amdgcn_rcpf((float)d));
     int r = (int)(n - __umul24(q, d));  // callers: quotient < 2^16 (see udiv_rcp)
     if (r < 0) {
@@ -1385,10 +1314,6 @@ __device__ __forceinline__ unsigned udiv_small(unsigned n, unsigned d, unsigned 
     }
     rem = (unsigned)r;  // (the caller's own n - q * d compiled to a quarter-rate 32-bit multiply)
     return q;
-#else
-    rem = n % d;
-    return n / d;
-#endif
 }
 
 struct RayWalk {
@@ -1698,17 +1623,9 @@ hs_bin_kernel(FleetGeom geom, StreamState *__restrict__ state, const float2 *__r
     }
 }
 
-#ifndef S2D_TILE_MINW
-#define S2D_TILE_MINW 1
-#endif
-// Diagnostic build only (-DS2D_STAMPS): per-phase s_memtime sums of hs_tile_kernel, wave 0 of each
-// workgroup: [0] wait+clear, [1] raster, [2] apply, [3] tiles, [4] workgroup lifetime.
+// Clock sums of diagnostic builds (tools/build_diag.py uclk / mclk patch their stamps in; hs_get_diag_stamps
+// reads them): the product kernels never write them.
 __device__ unsigned long long g_stamps[8];
-#ifdef S2D_STAMPS
-#define S2D_STAMP(v) do { __builtin_amdgcn_sched_barrier(0); v = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define S2D_STAMP(v) do { } while (0)
-#endif
 
 // lds_barrier (defined with the match kernel): waits for this wave's LDS operations (lgkmcnt) but not
 // for its global loads/stores (__syncthreads' release fence would also drain vmcnt, serialising the
@@ -1730,7 +1647,7 @@ constexpr int LDS_STRIDE = TILE + 1;
 constexpr int TILE_WORDS = TILE_H * LDS_STRIDE;
 static_assert(TILE_H <= 32, "row masks are 32-bit");
 
-__global__ void __launch_bounds__(TILE_THREADS, S2D_TILE_MINW)
+__global__ void __launch_bounds__(TILE_THREADS, 1)
 hs_tile_kernel(FleetGeom geom, float *__restrict__ cells, const StreamState *__restrict__ state,
                const unsigned *__restrict__ rays_g, const uint4 *__restrict__ segs, const WorkItem *__restrict__ items,
                const WorkItem *__restrict__ wholes, const WorkQueue *__restrict__ wq, int max_points)
@@ -1741,8 +1658,6 @@ hs_tile_kernel(FleetGeom geom, float *__restrict__ cells, const StreamState *__r
     const unsigned n_total = n_items + wq->whole_used;
     const int lane = threadIdx.x;
     const float lf = geom.lf, lo = geom.lo;
-    unsigned long long ts0 = 0, ta = 0, tb = 0, tc = 0, td = 0, acc0 = 0, acc1 = 0, acc2 = 0, ntiles = 0;
-    S2D_STAMP(ts0);
     for (int k = lane; k < TILE_WORDS; k += TILE_THREADS) {
         s_hit[k] = 0xFFFFFFFFu;
         s_free[k] = 0xFFFFFFFFu;
@@ -1756,7 +1671,6 @@ hs_tile_kernel(FleetGeom geom, float *__restrict__ cells, const StreamState *__r
         if ((nxt.lvl_kind >> 8) == ITEM_TILE && (unsigned)lane < nxt.seg_count) sg_nxt = segs[nxt.seg_begin + lane];
     }
     for (; it < n_total; it += gridDim.x) {
-        S2D_STAMP(ta);
         const WorkItem item = nxt;
         const uint4 sg_cur = sg_nxt;
         const unsigned itn = it + gridDim.x;
@@ -1795,7 +1709,6 @@ hs_tile_kernel(FleetGeom geom, float *__restrict__ cells, const StreamState *__r
                 const int gy = Y0 + row;
                 if (((rowmask >> row) & 1u) && colok && gy < g.sy) cl[row] = tl[tile_cell(lane, row)];
             }
-            S2D_STAMP(tb);
             bool any = false;
             if (kind == ITEM_TILE) {
                 any = item.seg_count > 0;
@@ -1864,7 +1777,6 @@ hs_tile_kernel(FleetGeom geom, float *__restrict__ cells, const StreamState *__r
             if (tt == ntx * nty - 1 && itn < n_total && (nxt.lvl_kind >> 8) == ITEM_TILE &&
                 (unsigned)lane < nxt.seg_count)
                 sg_nxt = segs[nxt.seg_begin + lane];
-            S2D_STAMP(tc);
             if (__any(any)) {
                 unsigned touched = 0;
                 // apply: lane = column -> 256 B / 512 B coalesced row accesses
@@ -1900,27 +1812,8 @@ hs_tile_kernel(FleetGeom geom, float *__restrict__ cells, const StreamState *__r
                     atomicAdd(&const_cast<StreamState *>(state)[s].tot_touched, (unsigned long long)touched);
             }
             ++gen;
-            S2D_STAMP(td);
-            acc0 += tb - ta;
-            acc1 += tc - tb;
-            acc2 += td - tc;
-            ntiles += 1;
-            ta = td;
         }
     }
-#ifdef S2D_STAMPS
-    unsigned long long te;
-    S2D_STAMP(te);
-    if (lane == 0) {
-        atomicAdd(&g_stamps[0], acc0);
-        atomicAdd(&g_stamps[1], acc1);
-        atomicAdd(&g_stamps[2], acc2);
-        atomicAdd(&g_stamps[3], ntiles);
-        atomicAdd(&g_stamps[4], te - ts0);
-    }
-#else
-    (void)ts0; (void)acc0; (void)acc1; (void)acc2; (void)ntiles; (void)tb; (void)tc; (void)td;
-#endif
 }
 
 // ------------------------------------------------- k2 (default): per-(stream, level) grid update
@@ -1938,30 +1831,17 @@ hs_tile_kernel(FleetGeom geom, float *__restrict__ cells, const StreamState *__r
 // Fan groups: beams b with the same b / 64 (one wave's lanes in one pass) share a bounding box
 // (origin + their end cells, computed once); a tile outside a group's box is skipped by the whole
 // wave with one scalar test.  Laser scans are angle-ordered, so a group is a narrow fan.
-#ifndef S2D_UPD_STRIDE
-#define S2D_UPD_STRIDE 68
-#endif
 // LDS words per tile row: 16-B rows (the apply reads and restores a quad's marks as one uint4) whose
 // stride is not a multiple of 32 banks.  (67, odd, spreads a column of cells over all 32 banks of an
 // atomic's lane group instead of 8, but the raster's conflicts are mostly lanes on the SAME word, which
 // no stride changes -- tools/lds_sim.py: 2 % fewer raster LDS cycles -- and the unaligned quads cost the
 // apply more: measured 0.005 ms slower.)
-constexpr int UPD_STRIDE = S2D_UPD_STRIDE;
-#ifndef S2D_UPD_PRIO
-#define S2D_UPD_PRIO 0  // 1: hs_update_kernel raises a wave's priority by its share of the tile's fan groups (A/B)
-#endif
-#ifndef S2D_APPLY_FAST
-#define S2D_APPLY_FAST 1  // 0: every marked quad takes the full apply_cell sequence (A/B)
-#endif
-#ifndef S2D_UPD_TH
-#define S2D_UPD_TH (8 * S2D_UPD_WAVES)  // 32 rows with 4 waves, 64 with 8: every thread owns two quads of a tile
-#endif
-#ifndef S2D_UPD_MINB
-#define S2D_UPD_MINB 8  // __launch_bounds__ minimum: 8 waves per SIMD, which caps the VGPRs at 64 (full occupancy; with 8-wave
-                        // workgroups the value 4 let the compiler settle for 7 waves per SIMD, i.e. 3 workgroups per CU)
-#endif
-constexpr int UPD_TH = S2D_UPD_TH;                    // LDS tile height (a multiple of the storage TILE_H)
-static_assert(UPD_TH % TILE_H == 0, "an LDS tile covers whole storage tiles");
+constexpr int UPD_STRIDE = 68;
+constexpr int UPD_MINB = 8;  // __launch_bounds__ minimum: 8 waves per SIMD, which caps the VGPRs at 64 (full occupancy)
+constexpr int UPD_TH = 8 * UPD_WAVES;                 // LDS tile height: every thread owns two quads of a tile
+// (64-row LDS tiles over two storage tiles, with 8 waves, were measured and not kept:
+// profiles/r07/retired_build_variants.md; the ordinal plane's offsets below assume one storage tile)
+static_assert(UPD_TH == TILE_H, "an LDS tile is one storage tile");
 constexpr int UPD_TILE_WORDS = UPD_TH * UPD_STRIDE;   // one LDS mark array
 // r * UPD_STRIDE for a tile row r in [0, UPD_TH): the mask shows the compiler a 16-bit operand, so it
 // selects the full-rate v_mul_u32_u24 (r * 68 of an int of unknown range, and even __mul24 or a
@@ -1980,57 +1860,23 @@ constexpr int UPD_QUADS = TILE * UPD_TH / 4 / UPD_THREADS;  // apply quads per t
 // bit 4 + c "odd event word", bit 8 + c "hit" for its cells c = 0..3.
 // GridMapLogOddsFunctions (GridMapLogOdds.h:108-129) applied to one marked cell:
 // bit k of m set ? a : b, as a bitwise select on the float bits (no compare, no exec-mask branch)
-// The apply's stores: plain, or non-temporal (S2D_NT_STORE=1: a written cell is next touched one scan later,
-// after ~3.5 GB of other traffic, so keeping its line in L2 / the Infinity Cache buys nothing)
-#ifndef S2D_NT_STORE
-#define S2D_NT_STORE 0
-#endif
-typedef float nt_f4 __attribute__((ext_vector_type(4)));
-typedef int nt_i4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void upd_store(float4 *p, float4 v)
-{
-#if S2D_NT_STORE
-    const nt_f4 w = {v.x, v.y, v.z, v.w};
-    __builtin_nontemporal_store(w, reinterpret_cast<nt_f4 *>(p));
-#else
-    *p = v;
-#endif
-}
-__device__ __forceinline__ void upd_store(int4 *p, int4 v)
-{
-#if S2D_NT_STORE
-    const nt_i4 w = {v.x, v.y, v.z, v.w};
-    __builtin_nontemporal_store(w, reinterpret_cast<nt_i4 *>(p));
-#else
-    *p = v;
-#endif
-}
-__device__ __forceinline__ void upd_store(int *p, int v)
-{
-#if S2D_NT_STORE
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
+// The apply's stores, plain (non-temporal ones were measured and not kept: profiles/r07/retired_build_variants.md)
+__device__ __forceinline__ void upd_store(float4 *p, float4 v) { *p = v; }
+__device__ __forceinline__ void upd_store(int4 *p, int4 v) { *p = v; }
+__device__ __forceinline__ void upd_store(int *p, int v) { *p = v; }
 __device__ __forceinline__ float bit_select(unsigned m, int k, float a, float b)
 {
     const int sel = ((int)(m << (31 - k))) >> 31;  // 0 or -1
     return __int_as_float((__float_as_int(a) & sel) | (__float_as_int(b) & ~sel));
 }
 
-// A quad's mark bits as hs_update_kernel carries them from the mark read to the apply.
-//   S2D_PACK_PERM 1 (default): the quad's four event words gathered by two byte permutes and one bit-field
-//   insert -- bit 7 + 8 c set when cell c is unmarked (the top bit of W_NONE; an event 2 b + {0, 1} is below
-//   2^31), bit QB_OD(c) the low bit of its event (odd: freed before its first hit), bit 1 + c its hit bit
-//   (rotated out of the row's hit word), all other bits don't-care: 6 VALU per quad instead of ~24 for
-//   the twelve compares / selects / shifts that built the compact nibbles.  A hit cell is always marked
-//   (its atomicMin of 2 b), so the hit and odd bits need no masking with the marks.
-//   0: the compact nibbles, bits c / 4 + c / 8 + c = marked / odd / hit (A/B).
-#ifndef S2D_PACK_PERM
-#define S2D_PACK_PERM 1
-#endif
-#if S2D_PACK_PERM
+// A quad's mark bits as hs_update_kernel carries them from the mark read to the apply: the quad's four event
+// words gathered by two byte permutes and one bit-field insert -- bit 7 + 8 c set when cell c is unmarked (the
+// top bit of W_NONE; an event 2 b + {0, 1} is below 2^31), bit qb_od(c) the low bit of its event (odd: freed
+// before its first hit), bit 1 + c its hit bit (rotated out of the row's hit word), all other bits don't-care:
+// 6 VALU per quad instead of ~24 for the twelve compares / selects / shifts that build compact nibbles (bits
+// c / 4 + c / 8 + c = marked / odd / hit, as the ring kernel's apply still packs them).  A hit cell is always
+// marked (its atomicMin of 2 b), so the hit and odd bits need no masking with the marks.
 __device__ __forceinline__ constexpr int qb_un(int c) { return 7 + 8 * c; }
 __device__ __forceinline__ constexpr int qb_od(int c) { return c < 2 ? 16 + 8 * c : 8 * (c - 2); }
 __device__ __forceinline__ constexpr int qb_hit(int c) { return 1 + c; }
@@ -2051,24 +1897,6 @@ __device__ __forceinline__ unsigned qb_count(unsigned mb) { return __popc(~mb & 
 __device__ __forceinline__ bool qb_cell(unsigned mb, int c) { return !((mb >> qb_un(c)) & 1u); }
 __device__ __forceinline__ unsigned qb_hits(unsigned mb) { return mb & QB_HITMASK; }
 __device__ __forceinline__ float qb_sel_marked(unsigned mb, int c, float a, float b) { return bit_select(mb, qb_un(c), b, a); }
-#else
-__device__ __forceinline__ constexpr int qb_od(int c) { return 4 + c; }
-__device__ __forceinline__ constexpr int qb_hit(int c) { return 8 + c; }
-__device__ __forceinline__ unsigned qb_pack(uint4 m, unsigned hitw, int s)
-{
-    const unsigned h = (hitw >> s) & 15u;
-    const unsigned mk = (unsigned)(m.x != W_NONE) | ((unsigned)(m.y != W_NONE) << 1) | ((unsigned)(m.z != W_NONE) << 2) |
-                        ((unsigned)(m.w != W_NONE) << 3);
-    const unsigned od = (m.x & 1u) | ((m.y & 1u) << 1) | ((m.z & 1u) << 2) | ((m.w & 1u) << 3);
-    return mk | ((od & mk) << 4) | ((h & mk) << 8);
-}
-__device__ __forceinline__ bool qb_any(unsigned mb) { return (mb & 15u) != 0u; }
-__device__ __forceinline__ bool qb_all(unsigned mb) { return (mb & 15u) == 15u; }
-__device__ __forceinline__ unsigned qb_count(unsigned mb) { return __popc(mb & 15u); }
-__device__ __forceinline__ bool qb_cell(unsigned mb, int c) { return (mb >> c) & 1u; }
-__device__ __forceinline__ unsigned qb_hits(unsigned mb) { return (mb >> 8) & 15u; }
-__device__ __forceinline__ float qb_sel_marked(unsigned mb, int c, float a, float b) { return bit_select(mb, c, a, b); }
-#endif
 
 __device__ __forceinline__ float apply_cell(float l, unsigned odd, unsigned hit, float lf, float lo)
 {
@@ -2082,13 +1910,8 @@ __device__ __forceinline__ float apply_cell(float l, unsigned odd, unsigned hit,
 }
 
 // word offset of the quad at (c4, row) of the LDS tile (c4 % 4 == 0: 4 contiguous cells of a block row)
-// inside the level's tiled storage, relative to the LDS tile's first storage tile (rows past TILE_H
-// continue in the storage tile below)
-__device__ __forceinline__ int upd_off(int row, int c4, int tiles_x)
-{
-    if constexpr (UPD_TH == TILE_H) return tile_cell(c4, row);
-    return (row / TILE_H) * tiles_x * TILE_BLOCK_WORDS + tile_cell(c4, row % TILE_H);
-}
+// inside its storage tile
+__device__ __forceinline__ int upd_off(int row, int c4) { return tile_cell(c4, row); }
 
 constexpr int UPD_HIT_WORDS = UPD_TH * (TILE / 32);                  // one hit bit per tile cell
 constexpr int UPD_MARK_WORDS = (UPD_TILE_WORDS + UPD_HIT_WORDS + 3) & ~3;
@@ -2107,24 +1930,17 @@ __device__ __forceinline__ int lane_rank(unsigned long long m)  // set lanes bel
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
 }
 
-// Fan groups: the 64 beams a wave rasters together.  S2D_FAN_STRIDE 1 (default): 64 consecutive beams
+// Fan groups: the 64 beams a wave rasters together: 64 consecutive beams
 // (a 16 deg fan at 0.25 deg), lane l walking beam 2 (l % 32) + l / 32: each 32-lane half of an LDS
 // atomic (its banking group) spans the whole fan, and with the odd lanes walking backwards (see the
 // raster) the forward lanes of a half are 1 deg apart instead of 0.25 -- near the scan origin fewer
 // lanes land on one word (tools/lds_sim.py: 0.66 vs 0.75 of the consecutive order's raster LDS cycles).
-// 4: beams 256 G + 4 k + w for wave w of super-group G (a 64 deg fan, 1 deg apart), so that near the
-// scan origin the lanes of one LDS atomic address distinct cells -- measured slower (round 2, 0.82 vs
-// 0.78 ms): the wider fans lose more to culling than the conflicts cost.
-#ifndef S2D_FAN_STRIDE
-#define S2D_FAN_STRIDE 1
-#endif
+// (Beams 256 G + 4 k + w for wave w of super-group G -- a 64 deg fan, 1 deg apart, so that near the scan
+// origin the lanes of one LDS atomic address distinct cells -- measured slower (round 2, 0.82 vs 0.78 ms): the
+// wider fans lose more to culling than the conflicts cost.)
 __device__ __forceinline__ int fan_beam(int b0, int lane)  // b0 = 256 G + 64 w
 {
-#if S2D_FAN_STRIDE == 4
-    return (b0 & ~255) + 4 * lane + ((b0 >> 6) & 3);
-#else
     return b0 + 2 * (lane & 31) + (lane >> 5);
-#endif
 }
 __host__ __device__ constexpr int fan_groups(int max_points)
 {
@@ -2139,10 +1955,10 @@ constexpr int UPD_GROUP_WORDS = 4;  // LDS words per fan group: its bounding box
 // at 1081 beams, 8 instead of 7 workgroups per CU (the kernel's VGPRs allow 8).  RREG = 0: rays in LDS.
 // The rays are five named registers picked by selects on the wave-uniform fan-group index (an array
 // or a struct indexed by it ends up in scratch).
-constexpr int UPD_RREG = (1280 + UPD_THREADS - 1) / UPD_THREADS;  // scans of <= 1280 (4 waves) / 1536 (8) points
+constexpr int UPD_RREG = (1280 + UPD_THREADS - 1) / UPD_THREADS;  // scans of <= 1280 points
 static_assert(UPD_RREG <= 5, "five ray registers at most");
 template <int RREG>
-__global__ void __launch_bounds__(UPD_THREADS, S2D_UPD_MINB)
+__global__ void __launch_bounds__(UPD_THREADS, UPD_MINB)
 hs_update_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__restrict__ state,
                  const float2 *__restrict__ xy, int xy_stride, const float2 *__restrict__ mc, int mc_stride,
                  int stream_begin, int count, int max_points, const UpdList *__restrict__ wl,
@@ -2218,8 +2034,8 @@ hs_update_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__restr
             rr0 = k == 0 ? r : rr0;
             rr1 = k == 1 ? r : rr1;
             rr2 = k == 2 ? r : rr2;
-            rr3 = (RREG > 3 && k == 3) ? r : rr3;  // (8 waves: three registers)
-            rr4 = (RREG > 4 && k == 4) ? r : rr4;
+            rr3 = k == 3 ? r : rr3;
+            rr4 = k == 4 ? r : rr4;
         }
         int gx0 = x0, gy0 = y0, gx1 = x0, gy1 = y0;  // fan group box: origin + valid ends
         if (r != RAY_INVALID) {
@@ -2322,17 +2138,8 @@ hs_update_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__restr
             {
                 // this wave's groups (fi = wave + 4 k) among the first 64 that meet the tile, one set bit each:
                 // the loop visits only those (scalar find-first-set), then the groups past 64 test their box
-                unsigned long long gm = fm & ((UPD_WAVES == 8 ? 0x0101010101010101ull : 0x1111111111111111ull)
-                                              << (wave_beam0 >> 6));
+                unsigned long long gm = fm & (0x1111111111111111ull << (wave_beam0 >> 6));
                 int b0x = wave_beam0 + 64 * 64;  // groups >= 64 (scans of > 4096 points)
-                if constexpr (S2D_UPD_PRIO) {
-                    // the waves with more of this tile's groups issue first: the four meet at the tile's barrier,
-                    // so the busiest one is the workgroup's path (back to 0 after the raster)
-                    const int c = __popcll(gm);
-                    if (c >= 3) __builtin_amdgcn_s_setprio(3);
-                    else if (c == 2) __builtin_amdgcn_s_setprio(2);
-                    else if (c == 1) __builtin_amdgcn_s_setprio(1);
-                }
                 for (;;) {
                     int b0;
                     if (gm) {
@@ -2433,7 +2240,6 @@ hs_update_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__restr
                     if (k < scnt) upd_mark(lds_ptr(v & 0x3FFFFu), ev);
                 }
             }
-            if (S2D_UPD_PRIO) __builtin_amdgcn_s_setprio(0);
             if (__ballot(anyv != 0u) && lane == 0) s_any[buf] = (unsigned)(i + 1);
         }
         // every pending load first (only LDS work came after them): with the loads conditional the compiler
@@ -2453,16 +2259,13 @@ hs_update_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__restr
                 const unsigned mb = qb[j];
                 if (!qb_any(mb)) continue;
                 const int qi = qtid + j * UPD_THREADS;
-                const unsigned o = (unsigned)upd_off(qi >> 4, (qi & 15) << 2, g.tiles_x);
-                // the quad's ordinals, in 16-bit units from this tile block's plane: an LDS tile taller than a storage
-                // tile continues in the block below, whose plane is one block (2 x TILE_BLOCK_WORDS halves) further
-                const unsigned ou = UPD_TH == TILE_H ? o
-                                                     : o + (unsigned)((qi >> 4) / TILE_H * g.tiles_x * TILE_BLOCK_WORDS);
+                // (the quad's ordinals sit at the same offset, in 16-bit units, from this tile block's plane)
+                const unsigned o = (unsigned)upd_off(qi >> 4, (qi & 15) << 2);
                 float4 v = ql[j];
                 const float lv[4] = {v.x, v.y, v.z, v.w};
                 float nv[4];
                 unsigned uv[4];
-                if (S2D_APPLY_FAST && !__any(qb_hits(mb))) {
+                if (!__any(qb_hits(mb))) {
                     // no end cell in this quad slot of the whole wave (about three quarters of level 0's on the
                     // synthetic scans): every marked cell is free only -- updateSetFree alone, two VALU per cell
 #pragma unroll
@@ -2490,11 +2293,11 @@ hs_update_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__restr
                 // per marked cell (its unmarked cells were never read)
                 upd_store(reinterpret_cast<float4 *>(&pend_tl[o]), make_float4(nv[0], nv[1], nv[2], nv[3]));
                 if (qb_all(mb)) {
-                    *reinterpret_cast<uint2 *>(&tu[ou]) = make_uint2(uv[0] | (uv[1] << 16), uv[2] | (uv[3] << 16));
+                    *reinterpret_cast<uint2 *>(&tu[o]) = make_uint2(uv[0] | (uv[1] << 16), uv[2] | (uv[3] << 16));
                 } else {
 #pragma unroll
                     for (int c = 0; c < 4; ++c)
-                        if (qb_cell(mb, c)) tu[ou + (unsigned)c] = (unsigned short)uv[c];
+                        if (qb_cell(mb, c)) tu[o + (unsigned)c] = (unsigned short)uv[c];
                 }
                 touched += qb_count(mb);
             }
@@ -2505,7 +2308,7 @@ hs_update_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__restr
             if (s_any[buf] == (unsigned)(i + 1)) {
                 // thread owns quads q = tid + j * 256 (16 quads per 64-cell row); cells outside the map
                 // (padding of edge tiles) never carry marks
-                pend_tl = lvw + (size_t)(tx + ty * (UPD_TH / TILE_H) * g.tiles_x) * TILE_BLOCK_WORDS;
+                pend_tl = lvw + (size_t)(tx + ty * g.tiles_x) * TILE_BLOCK_WORDS;
 #pragma unroll
                 for (int j = 0; j < UPD_QUADS; ++j) {
                     const unsigned qi = (unsigned)qtid + j * UPD_THREADS;
@@ -2516,7 +2319,7 @@ hs_update_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__restr
                     const bool mk = qb_any(qb[j]);
                     // unsigned 32-bit offset: the load takes the scalar-base + VGPR-offset form, so nothing but
                     // the load itself writes its destination registers
-                    if (mk) ql[j] = *reinterpret_cast<const float4 *>(pend_tl + (unsigned)upd_off(row, c4, g.tiles_x));
+                    if (mk) ql[j] = *reinterpret_cast<const float4 *>(pend_tl + (unsigned)upd_off(row, c4));
                     // restore: the quad's event words (read by this thread only) and, by the first of
                     // the 8 lanes sharing it, the hit-bit word (its readers are this wave's lanes, whose
                     // read above precedes this write)
@@ -2547,37 +2350,30 @@ hs_update_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__restr
 // the previous one stopped: no clipping of the ray against the tile (round 3: ray_walk + walk_range + the
 // start division, ~150 VALU per (tile, fan group) visit), only the exit of the tile (one division by db
 // for the minor boundary, one by da for the minor steps taken).
-// Parts: part p of a level takes a contiguous range of rings (split by tile count, ring_split); its
+// Parts: part p of a level takes a contiguous range of rings (split by weight, ring_split_w); its
 // cursors start at the first step of each ray inside its first ring (ray_cursor).
 // Per ray two registers (scans of <= RING_GROUPS * 256 points; larger scans use hs_update_kernel<0>):
 //   consts  = da | db << 14 | (x step < 0) << 28 | (y step < 0) << 29 | x major << 30   (0: no ray)
 //   cursor  = i | q << 16: step i is next, q = its minor steps (i > da: the ray is done)
 // (da, db < 2^14: maps of at most 16384 cells per side, upd_ring_ok).
-// LDS tile height of the ring kernel: 32 rows with 256-thread workgroups (default), or 64 rows with 512-thread
-// workgroups (S2D_RING_TH=64: a ray crosses fewer tiles; the same LDS and registers per wave, 2 quads per
-// thread in the apply, 8 waves at every tile barrier)
-#ifndef S2D_RING_TH
-#define S2D_RING_TH 32
-#endif
-constexpr int RTH = S2D_RING_TH;
-constexpr int RTHREADS = RTH == 64 ? 512 : 256;
+// LDS tile height of the ring kernel: one storage tile, 256-thread workgroups (64 rows with 512-thread workgroups
+// were measured and not kept: profiles/r07/retired_build_variants.md; the apply's ordinal offsets assume one
+// storage tile per LDS tile)
+constexpr int RTH = TILE_H;
+constexpr int RTHREADS = 256;
 constexpr int RWAVES = RTHREADS / 64;
-static_assert(RTH % TILE_H == 0 && (RTH == 32 || RTH == 64), "ring tiles: 32 or 64 rows");
+static_assert(RTH == TILE_H, "a ring tile is one storage tile");
 constexpr int RTILE_WORDS = RTH * UPD_STRIDE;                       // one LDS mark array
 constexpr int RHIT_WORDS = RTH * (TILE / 32);                       // one hit bit per tile cell
 constexpr int RMARK_WORDS = (RTILE_WORDS + RHIT_WORDS + 3) & ~3;
 constexpr int RFIXED_WORDS = 2 * RMARK_WORDS + 4;                  // two mark buffers + 4 spare words; then fan boxes
 constexpr int RQUADS = TILE * RTH / 4 / RTHREADS;                   // apply quads per thread per tile
-constexpr unsigned long long RGROUP_MASK = RWAVES == 4 ? 0x1111111111111111ull : 0x0101010101010101ull;
+constexpr unsigned long long RGROUP_MASK = 0x1111111111111111ull;
 constexpr int RING_GROUPS = (5 * 256 + RTHREADS - 1) / RTHREADS;    // fan groups per lane: scans of <= 1280 points
 __host__ __device__ constexpr int ring_fan_groups(int max_points) { return ((max_points + RTHREADS - 1) / RTHREADS) * RWAVES; }
 __host__ __device__ constexpr int ring_shmem_words(int max_points) { return RFIXED_WORDS + UPD_GROUP_WORDS * ring_fan_groups(max_points); }
 // word offset of the quad at (c4, row) of the LDS tile in the level's tiled storage (see upd_off)
-__device__ __forceinline__ int ring_off(int row, int c4, int tiles_x)
-{
-    if constexpr (RTH == TILE_H) return tile_cell(c4, row);
-    return (row / TILE_H) * tiles_x * TILE_BLOCK_WORDS + tile_cell(c4, row % TILE_H);
-}
+__device__ __forceinline__ int ring_off(int row, int c4) { return tile_cell(c4, row); }
 constexpr unsigned CUR_DONE = 0xFFFFu;
 
 __device__ __forceinline__ unsigned ray_consts(int x0, int y0, unsigned r)
@@ -2710,27 +2506,6 @@ __device__ __forceinline__ void ring_visit(unsigned C, unsigned &S, unsigned b, 
     if (kk < nfree) upd_mark(lds_ptr(v & 0x3FFFFu), ev);
 }
 
-// The ring range [kb, ke) of part p of `parts` for a box of `total` tiles: parts split the tiles of the
-// box in ring order by count (every part's range is whole rings).
-__device__ __forceinline__ void ring_split(int p, int parts, int kmax, int ox, int oy, int tx0, int tx1, int ty0,
-                                           int ty1, int &kb, int &ke)
-{
-    kb = 0;
-    ke = kmax + 1;
-    if (parts <= 1) return;
-    const int total = tiles_within(kmax, ox, oy, tx0, tx1, ty0, ty1);
-    const int lo = (int)(((long long)total * p) / parts), hi = (int)(((long long)total * (p + 1)) / parts);
-    // kb: the first ring whose preceding rings hold >= lo tiles (p = 0: ring 0); ke likewise for hi
-    kb = p == 0 ? 0 : kmax + 1;
-    ke = p == parts - 1 ? kmax + 1 : kmax + 1;
-    for (int k = 0; k <= kmax; ++k) {
-        const int before = tiles_within(k - 1, ox, oy, tx0, tx1, ty0, ty1);
-        if (p > 0 && kb > kmax && before >= lo && k > 0) kb = k;
-        if (p < parts - 1 && ke > kmax && before >= hi && k > 0) ke = k;
-    }
-    if (ke < kb) ke = kb;
-}
-
 // block-wide exclusive scan over the ring kernel's RTHREADS threads (s_wave: RWAVES ints)
 __device__ __forceinline__ int ring_exscan(int v, int *s_wave, int *total)
 {
@@ -2755,17 +2530,13 @@ __device__ __forceinline__ int ring_exscan(int v, int *s_wave, int *total)
     return base + x - v;
 }
 
-// Weighted variant (default): ring k weighs RING_TILE_W per box tile plus one per ray that reaches it (the
-// rays' end rings are histogrammed in LDS, s_rh[RING_HIST]; rings past the last bin count in it).  Inner
-// rings hold few tiles but every ray's first steps, so a split by tiles alone left the inner part the
-// heaviest.  All threads call it (two block barriers); s_cut[2] receives [kb, ke).
+// The ring range [kb, ke) of part p of `parts` (every part's range is whole rings), split by weight: ring k
+// weighs RING_TILE_W per box tile plus one per ray that reaches it (the rays' end rings are histogrammed in LDS,
+// s_rh[RING_HIST]; rings past the last bin count in it).  Inner rings hold few tiles but every ray's first
+// steps, so a split by tiles alone left the inner part the heaviest.  All threads call it (two block barriers);
+// s_cut[2] receives [kb, ke).
 constexpr int RING_HIST = 128;
-#ifndef S2D_RING_SPLIT_TILES
-#define S2D_RING_SPLIT_TILES 0  // 1: split by tile count alone (A/B)
-#endif
-#ifndef S2D_RING_TILE_W
-#define S2D_RING_TILE_W 64
-#endif
+constexpr int RING_TILE_W = 64;
 __device__ __forceinline__ void ring_split_w(int p, int parts, int kmax, int ox, int oy, int tx0, int tx1, int ty0,
                                              int ty1, const unsigned *s_rh, int *s_wave, int *s_cut, int &kb, int &ke)
 {
@@ -2777,7 +2548,7 @@ __device__ __forceinline__ void ring_split_w(int p, int parts, int kmax, int ox,
         unsigned reach = 0;
         for (int j = kk; j < RING_HIST; ++j) reach += s_rh[j];
         const int tk = tiles_within(tid, ox, oy, tx0, tx1, ty0, ty1) - tiles_within(tid - 1, ox, oy, tx0, tx1, ty0, ty1);
-        w = S2D_RING_TILE_W * tk + (int)reach;
+        w = RING_TILE_W * tk + (int)reach;
     }
     if (tid == 0) {
         s_cut[0] = p == 0 ? 0 : kmax + 1;
@@ -2823,7 +2594,7 @@ struct RingIter {
     }
 };
 
-__global__ void __launch_bounds__(RTHREADS, S2D_UPD_MINB * 256 / RTHREADS)
+__global__ void __launch_bounds__(RTHREADS, UPD_MINB)
 hs_update_ring_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__restrict__ state,
                       const float2 *__restrict__ xy, int xy_stride, const float2 *__restrict__ mc, int mc_stride,
                       int stream_begin, int count, int max_points, const UpdList *__restrict__ wl,
@@ -2937,13 +2708,7 @@ hs_update_ring_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__
     const int tx1 = s_bbox[2] / TILE, ty1 = s_bbox[3] / RTH;
     const int kmax = max(max(ox - tx0, tx1 - ox), max(oy - ty0, ty1 - oy));
     int kb = 0, ke = kmax + 1;
-    if (parts > 1) {
-#if S2D_RING_SPLIT_TILES
-        ring_split(part, parts, kmax, ox, oy, tx0, tx1, ty0, ty1, kb, ke);
-#else
-        ring_split_w(part, parts, kmax, ox, oy, tx0, tx1, ty0, ty1, s_rh, s_wave, s_cut, kb, ke);
-#endif
-    }
+    if (parts > 1) ring_split_w(part, parts, kmax, ox, oy, tx0, tx1, ty0, ty1, s_rh, s_wave, s_cut, kb, ke);
     const int my_tiles = tiles_within(ke - 1, ox, oy, tx0, tx1, ty0, ty1) - tiles_within(kb - 1, ox, oy, tx0, tx1, ty0, ty1);
 #pragma unroll
     for (int k = 0; k < RING_GROUPS; ++k) Sk[k] = ray_cursor(Ck[k], kb, x0, y0, ox, oy);
@@ -3015,12 +2780,12 @@ hs_update_ring_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__
                 const unsigned mb = qb[j];
                 if (!(mb & 15u)) continue;
                 const int qi = tq + j * RTHREADS;
-                const unsigned o = (unsigned)ring_off(qi >> 4, (qi & 15) << 2, g.tiles_x);
+                const unsigned o = (unsigned)ring_off(qi >> 4, (qi & 15) << 2);
                 float4 v = ql[j];
                 const float lv[4] = {v.x, v.y, v.z, v.w};
                 float nv[4];
                 unsigned uv[4];
-                if (S2D_APPLY_FAST && !__any((mb >> 8) & 15u)) {
+                if (!__any((mb >> 8) & 15u)) {
                     // no end cell in this quad slot of the whole wave (three quarters of level 0's, tools'
                     // density model): every marked cell is free only -- updateSetFree alone
 #pragma unroll
@@ -3055,7 +2820,7 @@ hs_update_ring_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__
         if (i < my_tiles) {
             lds_barrier();  // tile i's marks complete
             if (s_any[buf] == (unsigned)(i + 1)) {
-                pend_tl = lvw + (size_t)(tx + ty * (RTH / TILE_H) * g.tiles_x) * TILE_BLOCK_WORDS;
+                pend_tl = lvw + (size_t)(tx + ty * g.tiles_x) * TILE_BLOCK_WORDS;
                 int tq = tid;
                 asm volatile("" : "+v"(tq));
 #pragma unroll
@@ -3069,7 +2834,7 @@ hs_update_ring_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__
                                         ((unsigned)(m.z != W_NONE) << 2) | ((unsigned)(m.w != W_NONE) << 3);
                     const unsigned od = (m.x & 1u) | ((m.y & 1u) << 1) | ((m.z & 1u) << 2) | ((m.w & 1u) << 3);
                     qb[j] = mk | ((od & mk) << 4) | ((h & mk) << 8);
-                    if (mk) ql[j] = *reinterpret_cast<const float4 *>(pend_tl + (unsigned)ring_off(row, c4, g.tiles_x));
+                    if (mk) ql[j] = *reinterpret_cast<const float4 *>(pend_tl + (unsigned)ring_off(row, c4));
                     if (mk) {
                         // "no mark" from an opaque register: a hoisted all-ones quad was held across the loop
                         // and spilled (its reload waited for the quad loads just issued)

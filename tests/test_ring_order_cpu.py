@@ -1,7 +1,7 @@
 """The tile order of hs_update_ring_kernel, restated in Python and checked on the CPU.
 
 The kernel keeps one cursor per ray and visits the tiles of a level's box in rings around the tile of the
-scan's begin cell (csrc/hector_kernels.hip: RingIter, ring_split, ray_cursor).  That is only correct if
+scan's begin cell (csrc/hector_kernels.hip: RingIter, ring_split_w, ray_cursor).  That is only correct if
 every ray meets its tiles in the visit order -- (ring k = Chebyshev distance in tiles, secondary distance
 s = min(|dx|, |dy|)) strictly increasing at every tile change along the Bresenham walk of
 OccGridMapBase.h:220-299 -- and if the enumeration yields every tile of the box exactly once.  Both are
@@ -80,6 +80,9 @@ def tiles_within(k, ox, oy, box):
 
 
 def ring_split(p, parts, kmax, ox, oy, box):
+    """Whole-ring ranges [kb, ke) by tile count.  (The kernel's ring_split_w cuts by weight instead; what is checked
+    below holds for any cut into whole-ring ranges.  The device twin of this one is parked with the other retired
+    variants: profiles/r07/retired_build_variants.patch.)"""
     kb, ke = 0, kmax + 1
     if parts <= 1:
         return kb, ke
@@ -97,7 +100,8 @@ def ring_split(p, parts, kmax, ox, oy, box):
 
 @pytest.fixture(params=[32, 64], ids=["th32", "th64"])
 def tile_h(request):
-    """The ring kernel's LDS tile height (S2D_RING_TH: 32 with 256-thread workgroups, 64 with 512)."""
+    """The ring kernel's LDS tile height: 32 as built; 64 (with 512-thread workgroups) was measured, not kept, and
+    its code is profiles/r07/retired_build_variants.patch.  The order property holds for any tile height."""
     global TH
     old, TH = TH, request.param
     yield request.param

@@ -13,8 +13,11 @@ round-3 clip kernel (run them with SLAM2D_UPD_KERNEL=clip).
 
   plain      WRONG RESULTS  hs_update_kernel marks with plain LDS stores instead of atomicMin
   hwexp      WRONG RESULTS  hs_match_kernel uses the hardware exp instead of (float)exp(double)
-  gmplain    WRONG RESULTS  gm_compute_kernel walks with plain LDS stores instead of atomicAdd
+  gmplain    WRONG RESULTS  gm_compute_kernel walks with plain LDS stores instead of atomicAdd (before round 7 this
+                            patched an unpacked walk that no build compiled: timings of gmplain from before then are
+                            those of the unpatched kernel)
   gmnowalk   WRONG RESULTS  gm_compute_kernel clips every line to the tile but skips the walk
+  gmnoacc    WRONG RESULTS  gm_compute_kernel runs no acc pass (prices the per-cell hit sums)
   nowalk     WRONG RESULTS  hs_update_kernel clips every ray to the tile but skips the Bresenham walk
   plfastatan WRONG RESULTS  pl_icp_kernel uses float atan / atan2 (prices the exact double ones)
   ktnorender WRONG RESULTS  kt_addscans_kernel clears, loads and stores its tiles but renders no item
@@ -84,9 +87,14 @@ PATCHES = {
                "__device__ __forceinline__ void upd_mark(unsigned *p, unsigned ev) "
                "{ *reinterpret_cast<volatile unsigned *>(p) = ev; }")],
     "hwexp": [(K, "    float odds = sdm_expf_tab(l, s_exptab);", "    float odds = __expf(l);")],
-    "gmplain": [("gmapping_kernels.hip", "        atomicAdd(reinterpret_cast<unsigned *>(pc), 1u); /* visits++ (:227-234) */ \\\n",
-                 "        *reinterpret_cast<volatile unsigned *>(pc) = 1u;                             \\\n")],
-    "gmnowalk": [("gmapping_kernels.hip", "            if (GM_PRICE == 3) return;\n", "            return;\n")],  # (= GM_PRICE=3)
+    "gmplain": [("gmapping_kernels.hip", "        atomicAdd(gm_lds_ptr(v & 0xFFFFu), 1u); /* visits++ (:227-234) */          \\\n",
+                 "        *reinterpret_cast<volatile unsigned *>(gm_lds_ptr(v & 0xFFFFu)) = 1u;              \\\n"),
+                ("gmapping_kernels.hip", "            if (i < steps) atomicAdd(gm_lds_ptr(v & 0xFFFFu), 1u);\n",
+                 "            if (i < steps) *reinterpret_cast<volatile unsigned *>(gm_lds_ptr(v & 0xFFFFu)) = 1u;\n")],
+    "gmnowalk": [("gmapping_kernels.hip", "            const int tda = (int)two_da, tdb = (int)two_db;\n",
+                  "            return;\n            const int tda = (int)two_da, tdb = (int)two_db;\n")],
+    "gmnoacc": [("gmapping_kernels.hip", "        if (s_anyh[it & 1]) {  // (a tile where no beam ends has no acc pass)\n",
+                 "        if (false && s_anyh[it & 1]) {\n")],
     "plfastatan": [("plicp_kernels.hip", '#include "detmath.h"\n',
                     '#include "detmath.h"\n#define sdm_atan2(y, x) ((double)atan2f((float)(y), (float)(x)))\n'
                     '#define sdm_atan(x) ((double)atanf((float)(x)))\n')],
@@ -109,9 +117,8 @@ PATCHES = {
     "noorigin": [(K, "                    if ((int)!met | (int)(lo_i > hi_i)) continue;\n",
                   "                    if (lo_i < 8) lo_i = 8;\n                    if (!met | (lo_i > hi_i)) continue;\n")],
     "nohitbit": [(K, "                    atomicOr(&hitb[c >> 5], 1u << (c & 31));\n", "                    (void)c;\n")],
-    "seqnochain": [(K, "                run = seq_chain_t<CW_STRIDE>(seqT + (CW_BUFS == 2 ? (j & 1) * CW_BUF : 0), lane, min(CW_PTS, n - j * CW_PTS),\n"
-                       "                                             run);\n",
-                    "                run = run + seqT[lane * CW_STRIDE];\n")],
+    "seqnochain": [(K, "            if (lane < 9) run = seq_chain_t<CW_STRIDE>(seqT, lane, min(CW_PTS, n - j * CW_PTS), run);\n",
+                    "            if (lane < 9) run = run + seqT[lane * CW_STRIDE];\n")],
     "frozen": [(K, "            for (int it = 0; it <= iters; ++it) {\n                if (in_regs) {",
                 "            for (int it = 0; it <= iters && false; ++it) {\n                if (in_regs) {")],
     "chainregs": [(K, "            b0 = row[i]; b1 = row[i + 1]; b2 = row[i + 2]; b3 = row[i + 3];\n",
@@ -125,16 +132,16 @@ PATCHES = {
     "mlds4": [(K, "    __shared__ float s_pose[2][POSE_WORDS];                             // a step's result, by parity\n",
                "    __shared__ float s_pose[2][POSE_WORDS];                             // a step's result, by parity\n"
                "    __shared__ float s_pad[300];\n    if (stream_begin < 0) s_pad[threadIdx.x] = 1.0f;\n")],
-    "noload": [(K, "                    if (mk) ql[j] = *reinterpret_cast<const float4 *>(pend_tl + (unsigned)upd_off(row, c4, g.tiles_x));\n",
+    "noload": [(K, "                    if (mk) ql[j] = *reinterpret_cast<const float4 *>(pend_tl + (unsigned)upd_off(row, c4));\n",
                 "                    if (mk) ql[j] = make_float4(0.0f, 0.0f, 0.0f, (float)row);\n")],
-    "nostore": [(K, "__device__ __forceinline__ void upd_store(float4 *p, float4 v)\n{\n#if S2D_NT_STORE",
-                 "__device__ __forceinline__ void upd_store(float4 *p, float4 v)\n{\n    if (v.x == 1234.5f) *p = v;\n    return;\n#if S2D_NT_STORE"),
-                (K, "__device__ __forceinline__ void upd_store(int4 *p, int4 v)\n{\n#if S2D_NT_STORE",
-                 "__device__ __forceinline__ void upd_store(int4 *p, int4 v)\n{\n    if (v.x == 1234) *p = v;\n    return;\n#if S2D_NT_STORE"),
-                (K, "__device__ __forceinline__ void upd_store(int *p, int v)\n{\n#if S2D_NT_STORE",
-                 "__device__ __forceinline__ void upd_store(int *p, int v)\n{\n    if (v == 1234) *p = v;\n    return;\n#if S2D_NT_STORE")],
-    "noord": [(K, "                if (qb_all(mb)) {\n                    *reinterpret_cast<uint2 *>(&tu[ou]) = make_uint2(uv[0] | (uv[1] << 16), uv[2] | (uv[3] << 16));\n                } else {\n#pragma unroll\n                    for (int c = 0; c < 4; ++c)\n                        if (qb_cell(mb, c)) tu[ou + (unsigned)c] = (unsigned short)uv[c];\n                }\n", "")],
-    "ordbm": [(K, "                if (qb_all(mb)) {\n                    *reinterpret_cast<uint2 *>(&tu[ou]) = make_uint2(uv[0] | (uv[1] << 16), uv[2] | (uv[3] << 16));\n                } else {\n#pragma unroll\n                    for (int c = 0; c < 4; ++c)\n                        if (qb_cell(mb, c)) tu[ou + (unsigned)c] = (unsigned short)uv[c];\n                }\n", "                (void)uv;\n"),
+    "nostore": [(K, "__device__ __forceinline__ void upd_store(float4 *p, float4 v) { *p = v; }\n",
+                 "__device__ __forceinline__ void upd_store(float4 *p, float4 v) { if (v.x == 1234.5f) *p = v; }\n"),
+                (K, "__device__ __forceinline__ void upd_store(int4 *p, int4 v) { *p = v; }\n",
+                 "__device__ __forceinline__ void upd_store(int4 *p, int4 v) { if (v.x == 1234) *p = v; }\n"),
+                (K, "__device__ __forceinline__ void upd_store(int *p, int v) { *p = v; }\n",
+                 "__device__ __forceinline__ void upd_store(int *p, int v) { if (v == 1234) *p = v; }\n")],
+    "noord": [(K, "                if (qb_all(mb)) {\n                    *reinterpret_cast<uint2 *>(&tu[o]) = make_uint2(uv[0] | (uv[1] << 16), uv[2] | (uv[3] << 16));\n                } else {\n#pragma unroll\n                    for (int c = 0; c < 4; ++c)\n                        if (qb_cell(mb, c)) tu[o + (unsigned)c] = (unsigned short)uv[c];\n                }\n", "")],
+    "ordbm": [(K, "                if (qb_all(mb)) {\n                    *reinterpret_cast<uint2 *>(&tu[o]) = make_uint2(uv[0] | (uv[1] << 16), uv[2] | (uv[3] << 16));\n                } else {\n#pragma unroll\n                    for (int c = 0; c < 4; ++c)\n                        if (qb_cell(mb, c)) tu[o + (unsigned)c] = (unsigned short)uv[c];\n                }\n", "                (void)uv;\n"),
               (K, "                touched += qb_count(mb);\n            }\n            pend_tl = nullptr;\n",
                "                touched += qb_count(mb);\n            }\n            {\n                unsigned bm = 0u;\n#pragma unroll\n"
                "                for (int j = 0; j < UPD_QUADS; ++j) {\n                    const unsigned u = ~qb[j] & QB_UNMASK;\n"
@@ -143,7 +150,7 @@ PATCHES = {
                "                if (__any(bm != 0u)) {\n                    tu[qtid] = (unsigned short)bm;\n"
                "                    if (lane == 0) *reinterpret_cast<uint4 *>(&pend_tl[ORD_OFF + 512 + 4 * (qtid >> 6)]) = "
                "make_uint4(mark_free, (unsigned)(size_t)pend_tl, 0u, 0u);\n                }\n            }\n            pend_tl = nullptr;\n")],
-    "ordbm2": [(K, "                if (qb_all(mb)) {\n                    *reinterpret_cast<uint2 *>(&tu[ou]) = make_uint2(uv[0] | (uv[1] << 16), uv[2] | (uv[3] << 16));\n                } else {\n#pragma unroll\n                    for (int c = 0; c < 4; ++c)\n                        if (qb_cell(mb, c)) tu[ou + (unsigned)c] = (unsigned short)uv[c];\n                }\n", "                (void)uv;\n"),
+    "ordbm2": [(K, "                if (qb_all(mb)) {\n                    *reinterpret_cast<uint2 *>(&tu[o]) = make_uint2(uv[0] | (uv[1] << 16), uv[2] | (uv[3] << 16));\n                } else {\n#pragma unroll\n                    for (int c = 0; c < 4; ++c)\n                        if (qb_cell(mb, c)) tu[o + (unsigned)c] = (unsigned short)uv[c];\n                }\n", "                (void)uv;\n"),
                (K, "                touched += qb_count(mb);\n            }\n            pend_tl = nullptr;\n",
                 "                touched += qb_count(mb);\n            }\n            {\n                unsigned bm = 0u;\n#pragma unroll\n"
                 "                for (int j = 0; j < UPD_QUADS; ++j) {\n                    const unsigned u = ~qb[j] & QB_UNMASK;\n"
@@ -153,8 +160,8 @@ PATCHES = {
     "valu100": [(K, "        const int X0 = tx * TILE, Y0 = ty * UPD_TH;\n",
                  "        const int X0 = tx * TILE, Y0 = ty * UPD_TH;\n"
                  "        { float dmy_; asm volatile(\".rept 100\\n\\tv_add_f32 %0, %1, %2\\n\\t.endr\" : \"=v\"(dmy_) : \"v\"((float)X0), \"v\"((float)Y0)); }\n")],
-    "ordfull": [(K, "                if (qb_all(mb)) {\n                    *reinterpret_cast<uint2 *>(&tu[ou]) = make_uint2(uv[0] | (uv[1] << 16), uv[2] | (uv[3] << 16));\n                } else {\n#pragma unroll\n                    for (int c = 0; c < 4; ++c)\n                        if (qb_cell(mb, c)) tu[ou + (unsigned)c] = (unsigned short)uv[c];\n                }\n",
-                 "                *reinterpret_cast<uint2 *>(&tu[ou]) = make_uint2(uv[0] | (uv[1] << 16), uv[2] | (uv[3] << 16));\n")],
+    "ordfull": [(K, "                if (qb_all(mb)) {\n                    *reinterpret_cast<uint2 *>(&tu[o]) = make_uint2(uv[0] | (uv[1] << 16), uv[2] | (uv[3] << 16));\n                } else {\n#pragma unroll\n                    for (int c = 0; c < 4; ++c)\n                        if (qb_cell(mb, c)) tu[o + (unsigned)c] = (unsigned short)uv[c];\n                }\n",
+                 "                *reinterpret_cast<uint2 *>(&tu[o]) = make_uint2(uv[0] | (uv[1] << 16), uv[2] | (uv[3] << 16));\n")],
     "uclk": [(K, "    for (int ii = 0; ii <= my_tiles; ++ii) {\n        const int i = __builtin_amdgcn_readfirstlane(ii);  // uniform (the compiler had put it in a VGPR)\n        const int qtid = tid;",
               "    unsigned long long u_r = 0, u_w = 0, u_a = 0, u_b = 0, u_m = 0, u_t = __builtin_amdgcn_s_memtime();\n"
               "#define UCLK(acc) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); acc += t_ - u_t; u_t = t_; } while (0)\n"
@@ -173,13 +180,13 @@ PATCHES = {
     "mclk": [(K, "template <int NP, bool BIG>\n__device__ __forceinline__ void gn_step_cw(",
               "extern __device__ unsigned long long g_stamps[8];\n__shared__ unsigned long long s_mk[8];\n"
               "template <int NP, bool BIG>\n__device__ __forceinline__ void gn_step_cw("),
-             (K, "    if (S2D_PRECHAIN_PRIO) __builtin_amdgcn_s_setprio(S2D_PRECHAIN_PRIO);\n    if (wave != cw) {\n        // the moved points' neighbourhoods",
+             (K, "    __builtin_amdgcn_s_setprio(PRECHAIN_PRIO);\n    if (wave != cw) {\n        // the moved points' neighbourhoods",
               "    unsigned long long mk_t0 = __builtin_amdgcn_s_memtime(), mk_t1 = 0, mk_t2 = 0, mk_pa = 0, mk_pb = 0, mk_pc = 0; bool mk_big = false;\n"
-              "    if (S2D_PRECHAIN_PRIO) __builtin_amdgcn_s_setprio(S2D_PRECHAIN_PRIO);\n    if (wave != cw) {\n        // the moved points' neighbourhoods"),
-             (K, "            lds_barrier();\n            if (lane < 9)\n                run = seq_chain_t<CW_STRIDE>(",
-              "            lds_barrier();\n            if (j == 0) mk_t1 = __builtin_amdgcn_s_memtime();\n            if (lane < 9)\n                run = seq_chain_t<CW_STRIDE>("),
-             (K, "                                             run);\n        }\n    }\n    float *sp = s_pose[parity];\n    if (wave == cw) {\n        float s[9], H[9];",
-              "                                             run);\n        }\n        mk_t2 = __builtin_amdgcn_s_memtime();\n    }\n    float *sp = s_pose[parity];\n    if (wave == cw) {\n        float s[9], H[9];"),
+              "    __builtin_amdgcn_s_setprio(PRECHAIN_PRIO);\n    if (wave != cw) {\n        // the moved points' neighbourhoods"),
+             (K, "            lds_barrier();\n            if (lane < 9) run = seq_chain_t<CW_STRIDE>(",
+              "            lds_barrier();\n            if (j == 0) mk_t1 = __builtin_amdgcn_s_memtime();\n            if (lane < 9) run = seq_chain_t<CW_STRIDE>("),
+             (K, "n - j * CW_PTS), run);\n        }\n    }\n    float *sp = s_pose[parity];\n    if (wave == cw) {\n        float s[9], H[9];",
+              "n - j * CW_PTS), run);\n        }\n        mk_t2 = __builtin_amdgcn_s_memtime();\n    }\n    float *sp = s_pose[parity];\n    if (wave == cw) {\n        float s[9], H[9];"),
              (K, "    __syncthreads();\n    // (H stays in s_pose, read once at the level's end)\n    est[0] = sp[0];\n    est[1] = sp[1];\n    est[2] = sp[2];\n    cs = sp[3];\n    sn = sp[4];\n}\n\nconstexpr int MATCH_REG_PTS",
               "    if (wave == cw && lane == 0) {\n        const unsigned long long mk_t3 = __builtin_amdgcn_s_memtime();\n"
               "        s_mk[0] += mk_t1 - mk_t0; s_mk[1] += mk_t2 - mk_t1; s_mk[2] += mk_t3 - mk_t2;\n    }\n"
@@ -189,8 +196,8 @@ PATCHES = {
               "        mk_pa = __builtin_amdgcn_s_memtime();\n        if (first) {\n            // a level's first step"),
              (K, "        lds_barrier();\n    }\n    if (wave != cw) {\n        // chunk j = slot j",
               "        lds_barrier();\n    }\n    mk_pb = __builtin_amdgcn_s_memtime();\n    if (wave != cw) {\n        // chunk j = slot j"),
-             (K, "            lds_barrier();  // chunk j stored (two buffers: and the chain wave is done with chunk j - 1)\n",
-              "            lds_barrier();  // chunk j stored (two buffers: and the chain wave is done with chunk j - 1)\n            if (j == 0) mk_pc = __builtin_amdgcn_s_memtime();\n"),
+             (K, "            lds_barrier();  // chunk j stored\n",
+              "            lds_barrier();  // chunk j stored\n            if (j == 0) mk_pc = __builtin_amdgcn_s_memtime();\n"),
              (K, "        const int c0 = s_mcnt[0], c1 = s_mcnt[1], tot = c0 + c1 + s_mcnt[2];\n",
               "        const int c0 = s_mcnt[0], c1 = s_mcnt[1], tot = c0 + c1 + s_mcnt[2];\n        mk_big = tot >= 512;\n        if (tid == 0 && mk_big) s_mk[3] += 1ull;\n"),
              (K, "    load_exptab();\n    if (!fused) __syncthreads();",
@@ -212,10 +219,10 @@ def _mclkbar():
         if "mk_big = tot >= 512;" in b:
             b = b.replace("        if (tid == 0 && mk_big) s_mk[3] += 1ull;\n", "")
         out.append((fname, a, b))
-    out.append((K, "            if (CW_BUFS == 1 && (!CW_SHARE || j > 0)) lds_barrier();\n            lds_barrier();\n"
+    out.append((K, "            if (j > 0) lds_barrier();\n            lds_barrier();\n"
                    "            if (j == 0) mk_t1 = __builtin_amdgcn_s_memtime();\n",
                 "            const unsigned long long mk_b0 = __builtin_amdgcn_s_memtime();\n"
-                "            if (CW_BUFS == 1 && (!CW_SHARE || j > 0)) lds_barrier();\n            lds_barrier();\n"
+                "            if (j > 0) lds_barrier();\n            lds_barrier();\n"
                 "            if (j == 0) mk_t1 = __builtin_amdgcn_s_memtime();\n"
                 "            else if (lane == 0) s_mk[3] += __builtin_amdgcn_s_memtime() - mk_b0;\n"))
     return out
