@@ -493,6 +493,15 @@ int kt_set_scans(kt_ctx *c, int first, int count, const double *ranges, const do
     return KT_OK;
 }
 
+int kt_pool_device(kt_ctx *c, const double **d_ranges, const double **d_poses, int *max_scans)
+{
+    if (!c) return kfail(KT_EINVAL, "ctx is NULL");
+    if (d_ranges) *d_ranges = c->d_ranges;
+    if (d_poses) *d_poses = c->d_poses;
+    if (max_scans) *max_scans = c->max_scans;
+    return KT_OK;
+}
+
 int kt_match_batch_device(kt_ctx *c, int count, const int *d_query, const int *d_bbeg, const int *d_bidx,
                           int do_penalize, int do_refine, kt_result *d_res, void *hip_stream)
 {

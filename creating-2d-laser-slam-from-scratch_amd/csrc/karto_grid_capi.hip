@@ -1,0 +1,365 @@
+// karto_grid_capi.hip -- host runtime + extern "C" boundary (include/slam2d/karto_grid.h) of the Karto
+// occupancy-grid rebuild.  Every compute step runs in karto_grid_kernels.hip; without a usable HIP device
+// kg_create fails with KG_ENODEV (no CPU fallback).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "karto_grid_kernels.hip"
+
+using namespace s2d;
+
+namespace {
+thread_local std::string kg_err;
+
+int gfail(int code, const char *what, hipError_t e = hipSuccess)
+{
+    kg_err = what;
+    if (e != hipSuccess) {
+        kg_err += ": ";
+        kg_err += hipGetErrorString(e);
+    }
+    return code;
+}
+
+#define GCHK(expr)                                              \
+    do {                                                        \
+        hipError_t _e = (expr);                                 \
+        if (_e != hipSuccess) return gfail(KG_EHIP, #expr, _e); \
+    } while (0)
+
+double g_round(double v) { return v >= 0.0 ? std::floor(v + 0.5) : std::ceil(v - 0.5); }  // math::Round
+
+constexpr size_t KG_MAX_CELLS = (size_t)1 << 28;
+constexpr double KG_MAX_REACH = 1048576.0;  // range_threshold / resolution, cells
+constexpr int KG_MAX_SPLIT = 32;
+
+enum { G_BBOX, G_REDUCE, G_RAYS, G_TRACE, G_UPDATE, G_NUM };
+const char *const g_names[G_NUM] = {"kg_bbox_kernel", "kg_bbox_reduce_kernel", "kg_rays_kernel", "kg_trace_kernel",
+                                    "kg_update_kernel"};
+}  // namespace
+
+struct kg_ctx {
+    KgGeom g{};
+    int max_scans = 0, num_cus = 0;
+    int force_split = 0;  // SLAM2D_KG_SPLIT: workgroups per tile, overriding the rule (tests, A/B)
+    size_t max_cells = 0;
+    int width = 0, height = 0;  // the last build's map
+    double *d_ranges = nullptr, *d_poses = nullptr;  // staging of kg_build
+    double *d_boxes = nullptr, *d_box = nullptr, *h_box = nullptr;
+    int2 *d_rays = nullptr;
+    KgScan *d_scans = nullptr;
+    uint32_t *d_pass = nullptr, *d_hits = nullptr;
+    uint8_t *d_state = nullptr;
+    int8_t *d_ros = nullptr;
+    hipStream_t stream = nullptr, last = nullptr;
+    std::mutex mu;
+    bool timing = false;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_free;
+    std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> ev_used;
+    double acc_ms[G_NUM] = {};
+    int64_t acc_n[G_NUM] = {};
+};
+
+namespace {
+
+int kg_begin_event(kg_ctx *c, hipStream_t s, std::pair<hipEvent_t, hipEvent_t> &ev)
+{
+    if (!c->timing) return KG_OK;
+    if (!c->ev_free.empty()) {
+        ev = c->ev_free.back();
+        c->ev_free.pop_back();
+    } else {
+        GCHK(hipEventCreate(&ev.first));
+        GCHK(hipEventCreate(&ev.second));
+    }
+    GCHK(hipEventRecord(ev.first, s));
+    return KG_OK;
+}
+
+int kg_end_event(kg_ctx *c, hipStream_t s, int which, std::pair<hipEvent_t, hipEvent_t> &ev)
+{
+    GCHK(hipGetLastError());
+    if (!c->timing) return KG_OK;
+    GCHK(hipEventRecord(ev.second, s));
+    c->ev_used.push_back({which, ev});
+    return KG_OK;
+}
+
+#define KG_LAUNCH(which, ...)                    \
+    do {                                         \
+        std::pair<hipEvent_t, hipEvent_t> _ev{}; \
+        int _rc = kg_begin_event(c, s, _ev);     \
+        if (_rc != KG_OK) return _rc;            \
+        hipLaunchKernelGGL(__VA_ARGS__);         \
+        _rc = kg_end_event(c, s, which, _ev);    \
+        if (_rc != KG_OK) return _rc;            \
+    } while (0)
+
+// Workgroups per tile.  One owner per tile (plain stores, no memset) as soon as the tiles alone fill every
+// CU's four resident workgroups (the tile's 33 KB of LDS); below that the tiles' scan lists are split so that
+// about 4 * CUs workgroups run, never finer than 32 scans per workgroup.  The split is rounded up to 1, 2, 4 or
+// a multiple of 8: workgroups go to the 8 XCDs round-robin and the part is blockIdx % split, so each XCD's L2
+// then serves the rays of split / 8 parts only -- the supposed cause of what was measured, 15 parts 2.58 ms and
+// 16 parts 1.73 ms per rebuild (profiles/r07/karto_grid.md).
+int kg_split_rule(const kg_ctx *c, int ntiles, int count)
+{
+    if (c->force_split > 0) return std::min(c->force_split, KG_MAX_SPLIT);
+    const int want = 4 * c->num_cus;
+    if (ntiles >= want) return 1;
+    int split = (want + ntiles - 1) / ntiles;
+    split = std::max(1, std::min(split, (count + 31) / 32));
+    if (split > 4) split = (split + 7) & ~7;
+    else if (split == 3) split = 4;
+    return std::min(split, KG_MAX_SPLIT);
+}
+
+int kg_run(kg_ctx *c, int count, const double *d_ranges, const double *d_poses, kg_info *info, hipStream_t s)
+{
+    KgGeom &g = c->g;
+    c->width = c->height = 0;
+    c->last = s;
+    kg_info out{};
+    KG_LAUNCH(G_BBOX, kg_bbox_kernel, dim3(count), dim3(KG_THREADS), 0, s, g, d_ranges, d_poses, c->d_boxes);
+    KG_LAUNCH(G_REDUCE, kg_bbox_reduce_kernel, dim3(1), dim3(KG_THREADS), 0, s, count, c->d_boxes, c->d_box);
+    GCHK(hipMemcpyAsync(c->h_box, c->d_box, sizeof(double) * 4, hipMemcpyDeviceToHost, s));
+    GCHK(hipStreamSynchronize(s));  // the call's one synchronisation: the launches below are sized by the box
+    // ComputeDimensions (Karto.h:5816-5821)
+    const double w = g_round((c->h_box[2] - c->h_box[0]) * g.scale);
+    const double h = g_round((c->h_box[3] - c->h_box[1]) * g.scale);
+    out.offset_x = c->h_box[0];
+    out.offset_y = c->h_box[1];
+    const bool fits = w >= 0 && h >= 0 && w <= 2147483647.0 && h <= 2147483647.0;  // false for NaN too
+    out.width = fits ? (int)w : INT_MAX;
+    out.height = fits ? (int)h : INT_MAX;
+    if (!fits || (double)out.width * (double)out.height > (double)c->max_cells) {
+        out.status = KG_ERANGE;
+        if (info) *info = out;
+        return gfail(KG_ERANGE, "the map has more cells than max_cells (kg_info holds its dimensions)");
+    }
+    out.status = KG_OK;
+    if (info) *info = out;
+    c->width = out.width;
+    c->height = out.height;
+    if (out.width == 0 || out.height == 0) return KG_OK;
+
+    g.width = out.width;
+    g.height = out.height;
+    g.off_x = out.offset_x;
+    g.off_y = out.offset_y;
+    g.tiles_x = (g.width + KG_TILE - 1) / KG_TILE;
+    g.tiles_y = (g.height + KG_TILE - 1) / KG_TILE;
+    const int ntiles = g.tiles_x * g.tiles_y;
+    g.split = kg_split_rule(c, ntiles, count);
+    const size_t cells = (size_t)g.width * g.height;
+
+    KG_LAUNCH(G_RAYS, kg_rays_kernel, dim3(count), dim3(KG_THREADS), 0, s, g, d_ranges, d_poses, c->d_rays,
+              c->d_scans);
+    if (g.split > 1) {
+        GCHK(hipMemsetAsync(c->d_pass, 0, sizeof(uint32_t) * cells, s));
+        GCHK(hipMemsetAsync(c->d_hits, 0, sizeof(uint32_t) * cells, s));
+    }
+    KG_LAUNCH(G_TRACE, kg_trace_kernel, dim3((unsigned)(ntiles * g.split)), dim3(KG_THREADS), 0, s, g, count,
+              c->d_rays, c->d_scans, c->d_pass, c->d_hits);
+    const size_t groups = (cells + 15) / 16;
+    KG_LAUNCH(G_UPDATE, kg_update_kernel, dim3((unsigned)((groups + KG_THREADS - 1) / KG_THREADS)), dim3(KG_THREADS),
+              0, s, g, cells, c->d_pass, c->d_hits, c->d_state, c->d_ros);
+    return KG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *kg_last_error(void) { return kg_err.c_str(); }
+
+void kg_default_params(kg_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->resolution = 0.05;
+    p->maximum_range = 0.0;  // the caller's scan->range_max
+    p->occupancy_threshold = 0.1;
+    p->min_pass_through = 2;
+}
+
+int kg_create(kg_ctx **out, const kt_laser *L, const kg_params *p, int max_scans, size_t max_cells)
+{
+    if (!out) return gfail(KG_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (!L || !p) return gfail(KG_EINVAL, "NULL argument");
+    if (!(p->resolution > 0) || !std::isfinite(p->resolution))
+        return gfail(KG_EINVAL, "resolution must be > 0 (the reference throws on 0)");
+    if (!(p->maximum_range > 0)) return gfail(KG_EINVAL, "maximum_range must be set (> 0): the scan's range_max");
+    if (L->n_readings < 1 || L->n_readings > 4096) return gfail(KG_EINVAL, "n_readings must be in [1, 4096]");
+    if (!(L->range_threshold > 0) || !(L->range_threshold / p->resolution <= KG_MAX_REACH))
+        return gfail(KG_EINVAL, "range_threshold must be > 0 and at most 2^20 cells long");
+    if (max_scans < 1 || max_cells < 1 || max_cells > KG_MAX_CELLS)
+        return gfail(KG_EINVAL, "need max_scans >= 1 and 1 <= max_cells <= 2^28");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return gfail(KG_ENODEV, "no HIP device");
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
+        return gfail(KG_ENODEV, "no HIP device");
+    kg_ctx *c = new kg_ctx;
+    c->max_scans = max_scans;
+    c->max_cells = max_cells;
+    c->num_cus = std::max(1, prop.multiProcessorCount);
+    if (const char *e = getenv("SLAM2D_KG_SPLIT")) c->force_split = atoi(e);
+    KgGeom &g = c->g;
+    g.min_angle = L->minimum_angle;
+    g.ang_res = L->angular_resolution;
+    g.min_range = L->minimum_range;
+    g.range_thr = L->range_threshold;
+    g.max_range = p->maximum_range;
+    g.scale = 1.0 / p->resolution;
+    g.occ_thr = p->occupancy_threshold;
+    g.min_pass = p->min_pass_through;
+    g.n = L->n_readings;
+    g.split = 1;
+    hipError_t e;
+    if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamDefault)) != hipSuccess) {
+        delete c;
+        return gfail(KG_EHIP, "hipStreamCreate", e);
+    }
+    const size_t S = (size_t)max_scans, n = (size_t)g.n, cells = (max_cells + 15) & ~(size_t)15;
+    if ((e = hipMalloc(&c->d_ranges, sizeof(double) * S * n)) != hipSuccess ||
+        (e = hipMalloc(&c->d_poses, sizeof(double) * S * 3)) != hipSuccess ||
+        (e = hipMalloc(&c->d_boxes, sizeof(double) * S * 4)) != hipSuccess ||
+        (e = hipMalloc(&c->d_box, sizeof(double) * 4)) != hipSuccess ||
+        (e = hipHostMalloc(&c->h_box, sizeof(double) * 4)) != hipSuccess ||
+        (e = hipMalloc(&c->d_rays, sizeof(int2) * S * n)) != hipSuccess ||
+        (e = hipMalloc(&c->d_scans, sizeof(KgScan) * S)) != hipSuccess ||
+        (e = hipMalloc(&c->d_pass, sizeof(uint32_t) * cells)) != hipSuccess ||
+        (e = hipMalloc(&c->d_hits, sizeof(uint32_t) * cells)) != hipSuccess ||
+        (e = hipMalloc(&c->d_state, cells)) != hipSuccess || (e = hipMalloc(&c->d_ros, cells)) != hipSuccess) {
+        kg_destroy(c);
+        return gfail(KG_ENOMEM, "hipMalloc", e);
+    }
+    *out = c;
+    return KG_OK;
+}
+
+int kg_destroy(kg_ctx *c)
+{
+    if (!c) return KG_OK;
+    if (c->last) hipStreamSynchronize(c->last);
+    if (c->stream) hipStreamSynchronize(c->stream);
+    void *bufs[] = {c->d_ranges, c->d_poses, c->d_boxes, c->d_box, c->d_rays, c->d_scans,
+                    c->d_pass,   c->d_hits,  c->d_state, c->d_ros};
+    for (void *b : bufs) hipFree(b);
+    if (c->h_box) hipHostFree(c->h_box);
+    for (auto &p : c->ev_free) {
+        hipEventDestroy(p.first);
+        hipEventDestroy(p.second);
+    }
+    for (auto &p : c->ev_used) {
+        hipEventDestroy(p.second.first);
+        hipEventDestroy(p.second.second);
+    }
+    if (c->stream) hipStreamDestroy(c->stream);
+    delete c;
+    return KG_OK;
+}
+
+int kg_build_device(kg_ctx *c, int count, const double *d_ranges, const double *d_poses, kg_info *info,
+                    void *hip_stream)
+{
+    if (info) {
+        memset(info, 0, sizeof(*info));
+        info->status = KG_EINVAL;
+    }
+    if (!c) return gfail(KG_EINVAL, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (count == 0) return gfail(KG_EINVAL, "no scans: no grid (CreateFromScans returns NULL)");
+    if (count < 0 || count > c->max_scans) return gfail(KG_EINVAL, "count exceeds max_scans");
+    if (!d_ranges || !d_poses) return gfail(KG_EINVAL, "NULL argument");
+    return kg_run(c, count, d_ranges, d_poses, info, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
+int kg_build(kg_ctx *c, int count, const double *ranges, const double *poses, kg_info *info)
+{
+    if (info) {
+        memset(info, 0, sizeof(*info));
+        info->status = KG_EINVAL;
+    }
+    if (!c) return gfail(KG_EINVAL, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (count == 0) return gfail(KG_EINVAL, "no scans: no grid (CreateFromScans returns NULL)");
+    if (count < 0 || count > c->max_scans) return gfail(KG_EINVAL, "count exceeds max_scans");
+    if (!ranges || !poses) return gfail(KG_EINVAL, "NULL argument");
+    hipStream_t s = c->stream;
+    GCHK(hipMemcpyAsync(c->d_ranges, ranges, sizeof(double) * (size_t)c->g.n * count, hipMemcpyHostToDevice, s));
+    GCHK(hipMemcpyAsync(c->d_poses, poses, sizeof(double) * 3 * count, hipMemcpyHostToDevice, s));
+    int rc = kg_run(c, count, c->d_ranges, c->d_poses, info, s);
+    if (rc != KG_OK) return rc;
+    GCHK(hipStreamSynchronize(s));
+    return KG_OK;
+}
+
+int kg_get_map(kg_ctx *c, uint8_t *state, int8_t *ros, uint32_t *pass, uint32_t *hits)
+{
+    if (!c) return gfail(KG_EINVAL, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (c->last) GCHK(hipStreamSynchronize(c->last));
+    const size_t cells = (size_t)c->width * c->height;
+    if (cells == 0) return KG_OK;
+    if (state) GCHK(hipMemcpy(state, c->d_state, cells, hipMemcpyDeviceToHost));
+    if (ros) GCHK(hipMemcpy(ros, c->d_ros, cells, hipMemcpyDeviceToHost));
+    if (pass) GCHK(hipMemcpy(pass, c->d_pass, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost));
+    if (hits) GCHK(hipMemcpy(hits, c->d_hits, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost));
+    return KG_OK;
+}
+
+int kg_device_planes(kg_ctx *c, const uint8_t **d_state, const int8_t **d_ros, const uint32_t **d_pass,
+                     const uint32_t **d_hits)
+{
+    if (!c) return gfail(KG_EINVAL, "ctx is NULL");
+    if (d_state) *d_state = c->d_state;
+    if (d_ros) *d_ros = c->d_ros;
+    if (d_pass) *d_pass = c->d_pass;
+    if (d_hits) *d_hits = c->d_hits;
+    return KG_OK;
+}
+
+int kg_set_timing(kg_ctx *c, int enable)
+{
+    if (!c) return gfail(KG_EINVAL, "ctx is NULL");
+    c->timing = enable != 0;
+    return KG_OK;
+}
+
+int kg_num_kernels(void) { return G_NUM; }
+const char *kg_kernel_name(int i) { return (i >= 0 && i < G_NUM) ? g_names[i] : ""; }
+
+int kg_get_kernel_times(kg_ctx *c, double *ms_out, int64_t *launches_out, int reset)
+{
+    if (!c) return gfail(KG_EINVAL, "ctx is NULL");
+    GCHK(hipDeviceSynchronize());
+    for (auto &u : c->ev_used) {
+        float ms = 0;
+        GCHK(hipEventElapsedTime(&ms, u.second.first, u.second.second));
+        c->acc_ms[u.first] += ms;
+        c->acc_n[u.first] += 1;
+        c->ev_free.push_back(u.second);
+    }
+    c->ev_used.clear();
+    for (int i = 0; i < G_NUM; ++i) {
+        if (ms_out) ms_out[i] = c->acc_ms[i];
+        if (launches_out) launches_out[i] = c->acc_n[i];
+        if (reset) {
+            c->acc_ms[i] = 0;
+            c->acc_n[i] = 0;
+        }
+    }
+    return KG_OK;
+}
+
+}  // extern "C"

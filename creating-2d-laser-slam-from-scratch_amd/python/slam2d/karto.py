@@ -56,6 +56,7 @@ def _declare(L):
     L.kt_get_grid_info.argtypes = [vp, vp]
     L.kt_set_scans.argtypes = [vp, i, i, vp, vp]
     L.kt_set_scans_device.argtypes = [vp, i, i, vp, vp, vp]
+    L.kt_pool_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i)]
     L.kt_match_scan.argtypes = [vp, vp, vp, i, vp, vp, i, i, C.POINTER(KtResult)]
     L.kt_match_batch_device.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp]
     L.kt_window_exchange_words.restype = C.c_size_t
@@ -150,6 +151,13 @@ class ScanMatcher:
     def set_scans_device(self, first: int, count: int, d_ranges: int, d_poses: int, hip_stream: int = 0):
         self._check(self.L.kt_set_scans_device(self.h, first, count, C.c_void_p(d_ranges), C.c_void_p(d_poses),
                                                C.c_void_p(hip_stream or None)), "kt_set_scans_device")
+
+    def pool_device(self):
+        """(d_ranges, d_poses, max_scans): the pool's device arrays (kt_pool_device), e.g. for
+        karto_grid.OccupancyGridBuilder.create_from_scans_device after set_scans_device with corrected poses."""
+        r, p, m = C.c_void_p(), C.c_void_p(), C.c_int()
+        self._check(self.L.kt_pool_device(self.h, C.byref(r), C.byref(p), C.byref(m)), "kt_pool_device")
+        return int(r.value or 0), int(p.value or 0), int(m.value)
 
     def match_batch_device(self, count: int, d_query: int, d_base_begin: int, d_base_index: int, d_results: int,
                            doPenalize: bool = True, doRefineMatch: bool = True, hip_stream: int = 0):

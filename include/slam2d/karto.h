@@ -99,6 +99,10 @@ int kt_get_grid_info(kt_ctx *ctx, int *out);
 int kt_set_scans(kt_ctx *ctx, int first, int count, const double *ranges, const double *poses);
 int kt_set_scans_device(kt_ctx *ctx, int first, int count, const double *d_ranges, const double *d_poses,
                         void *hip_stream);
+/* The pool's device arrays (double[max_scans][n_readings], double[max_scans][3]), so that a host which
+ * keeps its graph's scans here can hand them to kg_build_device (karto_grid.h) without a second copy;
+ * any output may be NULL. */
+int kt_pool_device(kt_ctx *ctx, const double **d_ranges, const double **d_poses, int *max_scans);
 
 /* One MatchScan (host arrays, synchronous; uses pool slots 0 .. n_base). */
 int kt_match_scan(kt_ctx *ctx, const double *query_ranges, const double query_pose[3], int n_base,
