@@ -2006,7 +2006,7 @@ hs_update_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__restr
     const LevelGeom &g = geom.lv[lvl];
     // level 0: this step's DataContainer; levels >= 1: the stored one of the last match
     // (MapRepMultiMap::updateByScan, MapRepMultiMap.h:181-188; equal to this step's after a match)
-    const int n = lvl == 0 ? st.n : st.mc_n;
+    const int n = lvl == 0 ? st.n : st.mc_n;  // beams of the scan; the raster below runs on the nu distinct rays
     const int tid = threadIdx.x;
     float *lvw = cells + (size_t)s * geom.stream_words + g.word_offset;
 
@@ -2019,16 +2019,70 @@ hs_update_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__restr
     int bx0 = x0, by0 = y0, bx1 = x0, by1 = y0;
     unsigned long long L = 0, R = 0;
     const float2 *pts = lvl == 0 ? xy + (size_t)local * xy_stride : mc + (size_t)s * mc_stride;
+    // Ray setup.  A ray is its end cell alone (every ray starts at the common begin cell), so two beams with the
+    // same end cell walk the same cells: the later one can only repeat the earlier one's marks with larger
+    // events, and the mark words keep the minimum -- it changes no word and no hit bit.  At the coarse levels
+    // (points scaled by 1/2, 1/4) most neighbouring beams collapse onto one end cell.  So the raster runs on the
+    // distinct rays only: a beam is dropped when it is invalid or its ray equals its predecessor's (duplicates
+    // further apart, A B A, are kept -- about one per scan), and the nu survivors are packed in beam order into
+    // consecutive fan groups with the event codes 2 b, 2 b + 1 of their packed index b.  The tile loop reads an
+    // event as marked / its parity only, both of which depend on the order of the events alone, and the
+    // renumbering is monotone.  (profiles/r08/dedup_model.txt: 26 % of the walk steps and 19 % of the tile x
+    // group visits of the synthetic scans belong to duplicates; the gain measured: profiles/r08/ab_dedup.md.)
+    // The counters and the level box are taken over every valid beam, as the reference counts them.
+    // Thread t owns the consecutive beams [t per, (t + 1) per): one workgroup scan of its survivor count
+    // gives their packed index.  RREG > 0 keeps the thread's rays in registers across the scan and packs into
+    // the (still unused) mark buffers; RREG == 0 recomputes them and packs into rays[] (nothing reads rays[]
+    // before the scan, and a packed index never exceeds the beam's own).
+    static_assert(2 * UPD_MARK_WORDS >= UPD_RREG * UPD_THREADS, "the mark buffers hold the packed rays");
+    static_assert(UPD_THREADS == BIN_THREADS, "block_exscan scans 256 threads");
+    __shared__ int s_scan[UPD_WAVES];
+    const int per = RREG > 0 ? RREG : (n + UPD_THREADS - 1) / UPD_THREADS;
+    const int bb = tid * per;
+    unsigned *packed = RREG > 0 ? smem : rays;
+    const unsigned prev0 = (bb > 0 && bb <= n) ? make_ray(g, fr, pts[bb - 1]) : RAY_INVALID;
+    unsigned lr[RREG > 0 ? RREG : 1];
+    unsigned prev = prev0;
+    int keeps = 0;
+#pragma unroll RREG > 0 ? RREG : 1
+    for (int j = 0; j < per; ++j) {
+        const int b = bb + j;
+        const unsigned r = b < n ? make_ray(g, fr, pts[b]) : RAY_INVALID;
+        if (r != RAY_INVALID) {
+            const int x1 = (int)(r & 0xFFFFu), y1 = (int)(r >> 16);
+            bx0 = min(bx0, x1); by0 = min(by0, y1); bx1 = max(bx1, x1); by1 = max(by1, y1);
+            const int adx = abs(x1 - x0), ady = abs(y1 - y0);
+            L += (unsigned long long)(max(adx, ady) + 1);
+            R += 1;
+        }
+        const bool keep = (r != RAY_INVALID) & (r != prev);
+        if constexpr (RREG > 0) lr[j] = keep ? r : RAY_INVALID;
+        keeps += (int)keep;
+        prev = r;
+    }
+    int nu_v;
+    int pk = block_exscan(keeps, s_scan, &nu_v);
+    const int nu = __builtin_amdgcn_readfirstlane(nu_v);  // workgroup-uniform: the rays the tile loop draws
+    if constexpr (RREG > 0) {
+#pragma unroll
+        for (int j = 0; j < RREG; ++j)
+            if (lr[j] != RAY_INVALID) packed[pk++] = lr[j];
+    } else {
+        prev = prev0;
+        for (int j = 0; j < per; ++j) {
+            const int b = bb + j;
+            const unsigned r = b < n ? make_ray(g, fr, pts[b]) : RAY_INVALID;
+            if ((r != RAY_INVALID) & (r != prev)) packed[pk++] = r;
+            prev = r;
+        }
+    }
+    __syncthreads();
     // the wave's first beam in a scalar register: the fan-group loops and the ray-register selects below
     // then compile to scalar control (tid & ~63 in a VGPR made them divergent loops with exec-mask code)
     const int wave_beam0 = __builtin_amdgcn_readfirstlane(tid & ~63);
-    for (int b0 = wave_beam0; (b0 & ~(UPD_THREADS - 1)) < n; b0 += UPD_THREADS) {   // wave-uniform trip count
+    for (int b0 = wave_beam0; (b0 & ~(UPD_THREADS - 1)) < nu; b0 += UPD_THREADS) {   // wave-uniform trip count
         const int b = fan_beam(b0, lane);
-        unsigned r = RAY_INVALID;
-        if (b < n) {
-            r = make_ray(g, fr, pts[b]);
-            if constexpr (RREG == 0) rays[b] = r;
-        }
+        const unsigned r = b < nu ? packed[b] : RAY_INVALID;
         if constexpr (RREG > 0) {
             const int k = (int)((unsigned)b0 / UPD_THREADS);
             rr0 = k == 0 ? r : rr0;
@@ -2037,15 +2091,11 @@ hs_update_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__restr
             rr3 = k == 3 ? r : rr3;
             rr4 = k == 4 ? r : rr4;
         }
-        int gx0 = x0, gy0 = y0, gx1 = x0, gy1 = y0;  // fan group box: origin + valid ends
+        int gx0 = x0, gy0 = y0, gx1 = x0, gy1 = y0;  // fan group box: origin + its rays' ends
         if (r != RAY_INVALID) {
             const int x1 = (int)(r & 0xFFFFu), y1 = (int)(r >> 16);
             gx0 = min(gx0, x1); gy0 = min(gy0, y1); gx1 = max(gx1, x1); gy1 = max(gy1, y1);
-            const int adx = abs(x1 - x0), ady = abs(y1 - y0);
-            L += (unsigned long long)(max(adx, ady) + 1);
-            R += 1;
         }
-        bx0 = min(bx0, gx0); by0 = min(by0, gy0); bx1 = max(bx1, gx1); by1 = max(by1, gy1);
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) {
             gx0 = min(gx0, __shfl_xor(gx0, off, 64));
@@ -2069,13 +2119,15 @@ hs_update_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__restr
         atomicAdd(&state[s].tot_cells, L);
         atomicAdd(&state[s].tot_rays, R);
     }
+    if constexpr (RREG > 0) __syncthreads();  // every wave has taken its rays out of the mark buffers
     // both mark buffers start clean (afterwards each tile's readers restore what its raster marked)
     for (int k = tid; k < 2 * UPD_MARK_WORDS / 4; k += UPD_THREADS)
         reinterpret_cast<uint4 *>(smem)[k] = (k % (UPD_MARK_WORDS / 4)) < UPD_TILE_WORDS / 4
                                                  ? make_uint4(W_NONE, W_NONE, W_NONE, W_NONE)
                                                  : make_uint4(0u, 0u, 0u, 0u);
     if (tid < 2) s_any[tid] = 0u;
-    if (!__syncthreads_or(R != 0)) {  // no ray drawn on this level
+    __syncthreads();
+    if (nu == 0) {  // no ray drawn on this level (a valid beam always leaves a survivor)
         clk_stamp(geom.clk, 1, false);
         return;
     }
@@ -2087,7 +2139,7 @@ hs_update_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__restr
     unsigned touched = 0;
 
     const int ntx = tx1 - tx0 + 1, ntiles = ntx * (ty1 - ty0 + 1);
-    const int nfans = ((n + UPD_THREADS - 1) / UPD_THREADS) * (UPD_THREADS / 64);  // groups with a box in gbox
+    const int nfans = ((nu + UPD_THREADS - 1) / UPD_THREADS) * (UPD_THREADS / 64);  // groups with a box in gbox
     const int my_tiles = ntiles > part ? (ntiles - part + parts - 1) / parts : 0;
     // Two-stage pipeline over this workgroup's tiles t_i = part + i * parts, ONE barrier per tile:
     //   iteration i: raster tile i into buffer i & 1 -> apply tile i - 1 from registers (its cell
@@ -2146,7 +2198,7 @@ hs_update_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__restr
                         b0 = __builtin_ctzll(gm) << 6;
                         gm &= gm - 1ull;
                     } else {
-                        if ((b0x & ~(UPD_THREADS - 1)) >= n) break;
+                        if ((b0x & ~(UPD_THREADS - 1)) >= nu) break;
                         b0 = b0x;
                         b0x += UPD_THREADS;
                         const int4 gb = gbox[b0 >> 6];
@@ -2160,7 +2212,7 @@ hs_update_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__restr
                         const int k = (int)((unsigned)b0 / UPD_THREADS);
                         r = k == 0 ? rr0 : (k == 1 ? rr1 : (k == 2 ? rr2 : (k == 3 ? rr3 : rr4)));
                     }
-                    else r = b < n ? rays[b] : RAY_INVALID;
+                    else r = b < nu ? rays[b] : RAY_INVALID;
                     // the tests below are combined with bitwise ors: one divergent branch (exec-mask save,
                     // test, restore: SALU work) per early exit instead of one per condition
                     const int x1 = (int)(r & 0xFFFFu), y1 = (int)(r >> 16);
