@@ -41,6 +41,9 @@ def _declare(L):
                          C.POINTER(PlResult)]
     L.pl_icp_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pl_set_params.argtypes = [C.c_void_p, C.POINTER(PlParams)]
+    L.pl_icp_ldp.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.c_void_p, C.POINTER(PlResult)]
     L.pl_set_timing.argtypes = [C.c_void_p, C.c_int]
     L.pl_get_kernel_times.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L._pl_declared = True
@@ -92,6 +95,31 @@ class PLICP:
         self._check(self.L.pl_icp(self.h, ref.shape[0], float(angle_min), float(angle_inc),
                                   ref.ctypes.data_as(C.c_void_p), sens.ctypes.data_as(C.c_void_p),
                                   g.ctypes.data_as(C.c_void_p), C.byref(r)), "pl_icp")
+        return dict(x=np.array(r.x[:]), valid=bool(r.valid), iterations=r.iterations, nvalid=r.nvalid, error=r.error)
+
+    def set_params(self, params: PlParams):
+        """Replace the context's sm_params fields (pl_set_params); they are read on every call after it."""
+        self._check(self.L.pl_set_params(self.h, C.byref(params)), "pl_set_params")
+        self.params = params
+
+    def icp_ldp(self, theta, ref, sens, ref_valid=None, sens_valid=None, first_guess=(0.0, 0.0, 0.0)) -> dict:
+        """sm_icp on two LDPs as LaserScanToLDP builds them (pl_icp_ldp): shared theta[n], readings[n] and
+        valid[n] (None = reading > 0) per scan."""
+        theta = np.ascontiguousarray(theta, np.float64)
+        ref = np.ascontiguousarray(ref, np.float64)
+        sens = np.ascontiguousarray(sens, np.float64)
+        g = np.ascontiguousarray(first_guess, np.float64)
+        rv = None if ref_valid is None else np.ascontiguousarray(ref_valid, np.int32)
+        sv = None if sens_valid is None else np.ascontiguousarray(sens_valid, np.int32)
+        n = theta.shape[0]
+        if ref.shape[0] != n or sens.shape[0] != n or any(v is not None and v.shape[0] != n for v in (rv, sv)):
+            raise ValueError("theta, readings and valid arrays must have one length")
+        r = PlResult()
+        self._check(self.L.pl_icp_ldp(self.h, n, theta.ctypes.data_as(C.c_void_p), ref.ctypes.data_as(C.c_void_p),
+                                      rv.ctypes.data_as(C.c_void_p) if rv is not None else None,
+                                      sens.ctypes.data_as(C.c_void_p),
+                                      sv.ctypes.data_as(C.c_void_p) if sv is not None else None,
+                                      g.ctypes.data_as(C.c_void_p), C.byref(r)), "pl_icp_ldp")
         return dict(x=np.array(r.x[:]), valid=bool(r.valid), iterations=r.iterations, nvalid=r.nvalid, error=r.error)
 
     def icp_batch_device(self, count, n, angle_min, angle_inc, d_ref, d_sens, d_guess, d_results, hip_stream=0):

@@ -56,9 +56,10 @@ def trajectory(num_scans: int, phase: float) -> np.ndarray:
     return np.stack([x, y, th], axis=1)
 
 
-def cast_ranges(poses: np.ndarray, segs: np.ndarray, n_beams: int = N_BEAMS) -> np.ndarray:
-    """Exact ranges [T, n_beams] (inf when nothing within RANGE_MAX)."""
-    ang = beam_angles(n_beams)
+def cast_ranges(poses: np.ndarray, segs: np.ndarray, n_beams: int = N_BEAMS, angles: np.ndarray | None = None) -> np.ndarray:
+    """Exact ranges [T, n_beams] (inf when nothing within RANGE_MAX); angles = the n_beams beam angles
+    when they are not the sensor's own (beam_angles)."""
+    ang = beam_angles(n_beams) if angles is None else np.asarray(angles, np.float64)
     a = segs[:, 0, :]
     e = segs[:, 1, :] - segs[:, 0, :]
     out = np.empty((poses.shape[0], n_beams), dtype=np.float64)

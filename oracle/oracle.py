@@ -343,6 +343,11 @@ def plicp_lib():
         L.plo_icp.restype = _i
         L.plo_icp.argtypes = [C.POINTER(PlParams), _i, C.c_double, C.c_double, _p, _p, _p, _i, _p,
                               C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_double), _p]
+        L.plo_last_exit.restype = _i
+        L.plo_last_exit.argtypes = []
+        L.plo_icp_theta.restype = _i
+        L.plo_icp_theta.argtypes = [C.POINTER(PlParams), _i, C.c_double, C.c_double, _p, _p, _p, _p, _i, _p,
+                                    C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_double), _p]
         _PL = L
     return _PL
 
@@ -353,8 +358,14 @@ def pl_default_params() -> PlParams:
     return p
 
 
-def plicp(ref, sens, angle_min, angle_inc, first_guess=(0.0, 0.0, 0.0), params=None, reduce_threads=0):
-    """CPU restatement of CSM sm_icp (parity unpinned).  Returns dict(x, valid, iterations, nvalid, error)."""
+_PL_EXITS = {1: "converged", 2: "loop", 3: "max_it", 4: "few_corr", 5: "solve"}
+
+
+def plicp(ref, sens, angle_min, angle_inc, first_guess=(0.0, 0.0, 0.0), params=None, reduce_threads=0, theta=None):
+    """CPU restatement of CSM sm_icp (parity unpinned).  Returns dict(x, valid, iterations, nvalid, error,
+    hashes, exit): hashes = the correspondence hash of every completed iteration, exit = the way out of
+    the loop ("converged", "loop", "max_it", "few_corr", "solve").  theta = the LDP's own angles (else
+    angle_min + i * angle_inc)."""
     L = plicp_lib()
     p = params or pl_default_params()
     ref = np.ascontiguousarray(ref, np.float64)
@@ -362,10 +373,31 @@ def plicp(ref, sens, angle_min, angle_inc, first_guess=(0.0, 0.0, 0.0), params=N
     g = np.ascontiguousarray(first_guess, np.float64)
     x = np.zeros(3, np.float64)
     it, nv, err = _i(), _i(), C.c_double()
-    hashes = np.zeros(64, np.int32)
-    ok = L.plo_icp(C.byref(p), ref.shape[0], float(angle_min), float(angle_inc), _fp(ref), _fp(sens), _fp(g),
-                   reduce_threads, _fp(x), C.byref(it), C.byref(nv), C.byref(err), _fp(hashes))
-    return dict(x=x, valid=bool(ok), iterations=it.value, nvalid=nv.value, error=err.value)
+    hashes = np.full(64, -1, np.int32)   # the hashes are 31-bit: -1 = never written
+    n = ref.shape[0]
+    if theta is None:
+        ok = L.plo_icp(C.byref(p), n, float(angle_min), float(angle_inc), _fp(ref), _fp(sens), _fp(g),
+                       reduce_threads, _fp(x), C.byref(it), C.byref(nv), C.byref(err), _fp(hashes))
+    else:
+        theta = np.ascontiguousarray(theta, np.float64)
+        ok = L.plo_icp_theta(C.byref(p), n, 0.0, 0.0, _fp(theta), _fp(ref), _fp(sens), _fp(g),
+                             reduce_threads, _fp(x), C.byref(it), C.byref(nv), C.byref(err), _fp(hashes))
+    code = L.plo_last_exit()
+    # every iteration that reached the solve wrote its hash: all of them, but for the failing iteration
+    done = it.value - (0 if ok else 1)
+    assert np.all(hashes[:done] >= 0) and np.all(hashes[done:] == -1), (done, hashes)
+    # the hashes pin the exit the loop reports: a repeated last hash <=> "loop"; few_corr / solve <=> invalid
+    # (told apart by which test failed -- nvalid is the previous iteration's after few_corr)
+    ex = _PL_EXITS[code]
+    assert (ex in ("few_corr", "solve")) == (not ok)
+    assert (ex == "loop") == (bool(ok) and done > 0 and hashes[done - 1] in hashes[:done - 1])
+    return dict(x=x, valid=bool(ok), iterations=it.value, nvalid=nv.value, error=err.value, hashes=hashes[:done].copy(),
+                exit=ex)
+
+
+def plicp_theta(theta, ref, sens, first_guess=(0.0, 0.0, 0.0), params=None, reduce_threads=0):
+    """plicp on an LDP's own theta[] (plo_icp_theta): what pl_icp_ldp computes."""
+    return plicp(ref, sens, 0.0, 0.0, first_guess, params, reduce_threads, theta=theta)
 
 
 # ---------------------------------------------------------------------------------------------- Karto

@@ -247,11 +247,20 @@ static double plo_kth(double *v, int k, int idx)  /* idx-th smallest of v[0..k) 
     return v[idx];
 }
 
-/* sm_icp for one scan pair; returns valid (all_is_okay).  info: iterations, nvalid; error. */
+/* The way the last plo_icp / plo_icp_theta call of this thread left icp_loop: the tests assert which
+ * exits their cases take.  CONVERGED and MAX_IT differ only in the epsilon test of the last iteration,
+ * FEW_CORR and SOLVE only in which test failed, so the loop records it where it happens. */
+enum { PLO_EXIT_NONE = 0, PLO_EXIT_CONVERGED, PLO_EXIT_LOOP, PLO_EXIT_MAX_IT, PLO_EXIT_FEW_CORR, PLO_EXIT_SOLVE };
+static __thread int plo_exit = PLO_EXIT_NONE;
+int plo_last_exit(void) { return plo_exit; }
+
+/* sm_icp for one scan pair; returns valid (all_is_okay).  info: iterations, nvalid; error.
+ * trace_hashes (int[64] or NULL): the correspondence hash of every iteration that reached the solve. */
 int plo_icp_theta(const plo_params *p, int n, double angle_min, double angle_inc, const double *theta,
                   const double *ref_r, const double *sens_r, const double *first_guess, int reduce_threads,
                   double *x_out, int *iterations_out, int *nvalid_out, double *error_out, int *trace_hashes)
 {
+    plo_exit = PLO_EXIT_NONE;
     if (n < 2 || n > PLO_MAX_RAYS) return 0;
     plo_scan *ref = (plo_scan *)malloc(sizeof(plo_scan));
     plo_scan *sens = (plo_scan *)malloc(sizeof(plo_scan));
@@ -308,7 +317,7 @@ int plo_icp_theta(const plo_params *p, int n, double angle_min, double angle_inc
             ++ncorr;
             e[i] = plo_dist_to_segment(ref->px[b1], ref->py[b1], ref->px[b2], ref->py[b2], wx, wy);
         }
-        if (ncorr < 0.05 * n) { all_ok = 0; break; }
+        if (ncorr < 0.05 * n) { all_ok = 0; plo_exit = PLO_EXIT_FEW_CORR; break; }
         /* kill_outliers_trim */
         int k = 0;
         for (int i = 0; i < n; ++i) if (ok[i]) sorted[k++] = e[i];
@@ -357,7 +366,7 @@ int plo_icp_theta(const plo_params *p, int n, double angle_min, double angle_inc
         }
         double m[14];
         plo_reduce((const double (*)[14])terms, ok, n, reduce_threads, m);
-        if (!plo_gpc_solve(m, x_new)) { all_ok = 0; break; }
+        if (!plo_gpc_solve(m, x_new)) { all_ok = 0; plo_exit = PLO_EXIT_SOLVE; break; }
         /* pose_diff_d(x_new, x_old) */
         const double co = odm_cos(x_old[2]), so = odm_sin(x_old[2]);
         const double ddx = x_new[0] - x_old[0], ddy = x_new[1] - x_old[1];
@@ -366,10 +375,14 @@ int plo_icp_theta(const plo_params *p, int n, double angle_min, double angle_inc
         if (trace_hashes) trace_hashes[it] = (int)hashes[it];
         int loop = 0;
         for (int a = 0; a < it; ++a) if (hashes[a] == hashes[it]) loop = 1;
-        if (loop) break;
-        if (fabs(dl0) < p->epsilon_xy && fabs(dl1) < p->epsilon_xy && fabs(dl2) < p->epsilon_theta) break;
+        if (loop) { plo_exit = PLO_EXIT_LOOP; break; }
+        if (fabs(dl0) < p->epsilon_xy && fabs(dl1) < p->epsilon_xy && fabs(dl2) < p->epsilon_theta) {
+            plo_exit = PLO_EXIT_CONVERGED;
+            break;
+        }
         x_old[0] = x_new[0]; x_old[1] = x_new[1]; x_old[2] = x_new[2];
     }
+    if (plo_exit == PLO_EXIT_NONE) plo_exit = PLO_EXIT_MAX_IT;
     x_out[0] = x_new[0]; x_out[1] = x_new[1]; x_out[2] = x_new[2];
     if (iterations_out) *iterations_out = it + (it < max_it ? 1 : 0);
     if (nvalid_out) *nvalid_out = nvalid;
