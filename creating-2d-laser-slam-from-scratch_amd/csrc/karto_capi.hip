@@ -590,6 +590,16 @@ int kt_match_sharded_end_device(kt_ctx *c, int count, const int *d_bbeg, const i
                            c->sharded_binned);
 }
 
+int kt_copy_grid_device(kt_ctx *c, int slot, unsigned char *d_out, void *hip_stream)
+{
+    if (!c || !d_out) return kfail(KT_EINVAL, "NULL argument");
+    if (slot < 0 || slot >= c->slots) return kfail(KT_EINVAL, "slot out of range");
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    KCHK(hipMemcpyAsync(d_out, c->d_grids + (size_t)slot * c->g.grid_stride, (size_t)c->g.data_size,
+                        hipMemcpyDeviceToDevice, s));
+    return KT_OK;
+}
+
 int kt_set_timing(kt_ctx *c, int enable)
 {
     if (!c) return kfail(KT_EINVAL, "ctx is NULL");

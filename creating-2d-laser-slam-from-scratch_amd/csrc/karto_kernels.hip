@@ -787,7 +787,11 @@ kt_addscans_kernel(KtGeom g, KtPool P, const KtState *__restrict__ st, const int
     unsigned char *tileb = reinterpret_cast<unsigned char *>(tile);
     int pa = 0;
     while (pa < nb) {
-        if (tid == 0) {  // as many base scans as the item store holds (one always fits: <= 4 * 4096)
+        // As many base scans as the item store holds.  One base scan must fit, or the loop would not
+        // advance: a footprint of half <= 20 overlaps (1 + 40 / 64)^2 ~ 2.6 tiles on average (4 at the
+        // most), so the 4096 points kt_create admits stay near 10.8 k items, below KT_AS_ITEMS = 15360;
+        // the worst case 4 * 4096 would not fit, but needs every point within 20 cells of a tile corner.
+        if (tid == 0) {
             int tot = 0, pb = pa;
             while (pb < nb && tot + sscan[pb] <= KT_AS_ITEMS) tot += sscan[pb++];
             s_pass_end = pb;
@@ -1179,8 +1183,19 @@ kt_exchange_kernel(KtGeom g, KtState *st, double *resp, unsigned long long *posm
             x[0] = (long long)S.best_bits;
             x[1] = S.status == KT_ERANGE ? 1 : 0;
         }
-        for (int i = tid; i < nxy2; i += KT_THREADS) x[2 + i] = (long long)pm[i];
-        for (int i = tid; i < np; i += KT_THREADS) x[2 + nxy2 + i] = r[i];
+        // kt_coarse_kernel leaves posmax to kt_select_kernel, so the exported per-position maximum is taken
+        // here from this rank's responses (angle-major: position i's angles are nxy2 words apart)
+        const int nA = g.nang[0];
+        for (int i = tid; i < nxy2; i += KT_THREADS) {
+            double mx = 0.0;
+            for (int a = 0; a < nA; ++a) {
+                const long long v = r[(size_t)a * nxy2 + i];
+                x[2 + nxy2 + (size_t)a * nxy2 + i] = v;
+                mx = kt_max(mx, __longlong_as_double(v));
+            }
+            pm[i] = kt_bits(mx);
+            x[2 + i] = (long long)kt_bits(mx);
+        }
     } else {
         if (tid == 0) {
             S.best_bits = (unsigned long long)x[0];

@@ -63,6 +63,7 @@ def _declare(L):
     L.kt_window_exchange_words.argtypes = [vp]
     L.kt_match_sharded_begin_device.argtypes = [vp, i, vp, vp, vp, i, i, i, vp, vp]
     L.kt_match_sharded_end_device.argtypes = [vp, i, vp, vp, i, i, vp, vp, vp]
+    L.kt_copy_grid_device.argtypes = [vp, i, vp, vp]
     L.kt_set_timing.argtypes = [vp, i]
     L.kt_kernel_name.restype = C.c_char_p
     L.kt_kernel_name.argtypes = [i]
@@ -204,6 +205,17 @@ class ScanMatcher:
         allreduce_window(x, group)
         self.match_sharded_end_device(count, d_base_begin, d_base_index, x.data_ptr(), d_results, doPenalize,
                                       doRefineMatch, hs)
+
+    def grid(self, slot: int = 0, hip_stream: int = 0) -> np.ndarray:
+        """Diagnostic: match slot `slot`'s correlation grid [height, width_step] (kt_copy_grid_device): the
+        AddScans result between match_sharded_begin_device and match_sharded_end_device, all zero after
+        any finished match."""
+        import torch
+        out = torch.empty(self.info["data_size"], dtype=torch.uint8, device="cuda")
+        self._check(self.L.kt_copy_grid_device(self.h, slot, C.c_void_p(out.data_ptr()),
+                                               C.c_void_p(hip_stream or None)), "kt_copy_grid_device")
+        torch.cuda.synchronize()
+        return out.cpu().numpy().reshape(-1, self.info["ws"])
 
     def set_timing(self, on: bool):
         self._check(self.L.kt_set_timing(self.h, 1 if on else 0), "kt_set_timing")

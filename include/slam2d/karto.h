@@ -135,6 +135,12 @@ int kt_match_sharded_end_device(kt_ctx *ctx, int count, const int *d_base_begin,
                                 int do_penalize, int do_refine, const int64_t *d_exchange, kt_result *d_results,
                                 void *hip_stream);
 
+/* Diagnostic: copy the data_size bytes (kt_get_grid_info) of match slot `slot`'s correlation grid to
+ * d_out (device memory, stream-ordered).  The grid holds the AddScans result between
+ * kt_match_sharded_begin_device and kt_match_sharded_end_device; after any finished match it is all
+ * zero (the footprints are cleared for the slot's next match). */
+int kt_copy_grid_device(kt_ctx *ctx, int slot, unsigned char *d_out, void *hip_stream);
+
 int kt_set_timing(kt_ctx *ctx, int enable);
 /* Accumulated device time per kernel: names kt_kernel_name(i), i < kt_num_kernels(). */
 int kt_num_kernels(void);

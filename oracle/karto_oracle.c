@@ -673,3 +673,44 @@ int ko_build_grid(const ko_laser *L, const ko_params *p, const double q_pose[3],
     free(m.g.kernel);
     return valid ? 0 : -3;
 }
+
+/* Test hook: per base scan, the number of points ko_add_scan would smear for this query pose -- the
+ * points ko_find_valid marks valid that lie in the ROI, counted before the "already occupied" skip.
+ * Returns their sum, or a negative error. */
+int ko_count_valid(const ko_laser *L, const ko_params *p, const double q_pose[3], int n_base, const double *b_ranges,
+                   const double *b_poses, int *per_base)
+{
+    ko_matcher m;
+    memset(&m, 0, sizeof(m));
+    m.p = p;
+    int rc = ko_geom_init(p, L, &m.g);
+    if (rc) return rc;
+    free(m.g.kernel);
+    unsigned char *valid = (unsigned char *)malloc((size_t)L->n_readings + 1);
+    if (!valid) return -3;
+    m.gox = q_pose[0] - (0.5 * (m.g.grid_size - 1) * m.g.res);
+    m.goy = q_pose[1] - (0.5 * (m.g.grid_size - 1) * m.g.res);
+    int total = 0;
+    for (int b = 0; b < n_base; b++) {
+        ko_scan s;
+        memset(&s, 0, sizeof(s));
+        int cnt = 0;
+        if (ko_scan_init(&s, L, b_ranges + (size_t)b * L->n_readings, b_poses + 3 * b)) {
+            ko_scan_free(&s);
+            free(valid);
+            return -3;
+        }
+        ko_find_valid(&s, q_pose[0], q_pose[1], valid);
+        for (int k = 0; k < s.npts; k++) {
+            if (!valid[k]) continue;
+            int gx, gy;
+            ko_w2g(&m, s.px[k], s.py[k], m.gox, m.goy, &gx, &gy);
+            if (gx >= 0 && gx < m.g.grid_size && gy >= 0 && gy < m.g.grid_size) cnt++;
+        }
+        ko_scan_free(&s);
+        if (per_base) per_base[b] = cnt;
+        total += cnt;
+    }
+    free(valid);
+    return total;
+}

@@ -436,6 +436,8 @@ def karto_lib():
         L.ko_coarse_responses.argtypes = [C.POINTER(KtLaser), C.POINTER(KtParams), _p, _p, _i, _p, _p, _i, _p]
         L.ko_build_grid.restype = _i
         L.ko_build_grid.argtypes = [C.POINTER(KtLaser), C.POINTER(KtParams), _p, _i, _p, _p, _p]
+        L.ko_count_valid.restype = _i
+        L.ko_count_valid.argtypes = [C.POINTER(KtLaser), C.POINTER(KtParams), _p, _i, _p, _p, _p]
         _KO = L
     return _KO
 
@@ -491,3 +493,16 @@ def karto_build_grid(laser: KtLaser, params: KtParams, q_pose, b_ranges, b_poses
     if rc:
         raise RuntimeError(f"ko_build_grid: {rc}")
     return out.reshape(info["width"], info["ws"])
+
+
+def karto_count_valid(laser: KtLaser, params: KtParams, q_pose, b_ranges, b_poses) -> np.ndarray:
+    """Per base scan, the points AddScan would smear for this query pose (valid and in the ROI; test hook)."""
+    b = np.ascontiguousarray(b_ranges, np.float64).reshape(-1, laser.n_readings)
+    bp = np.ascontiguousarray(b_poses, np.float64).reshape(-1, 3)
+    qp = np.ascontiguousarray(q_pose, np.float64)
+    per = np.zeros(max(1, b.shape[0]), np.int32)
+    rc = karto_lib().ko_count_valid(C.byref(laser), C.byref(params), _fp(qp), b.shape[0], _fp(b), _fp(bp), _fp(per))
+    if rc < 0:
+        raise RuntimeError(f"ko_count_valid: {rc}")
+    assert rc == int(per[:b.shape[0]].sum())
+    return per[:b.shape[0]]

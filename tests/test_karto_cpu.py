@@ -150,3 +150,109 @@ def test_sharded_window_exchange_gloo(world):
     for r in range(world):
         got = np.frombuffer(res[r], np.float64)
         assert np.array_equal(got.view(np.int64), want.view(np.int64)), r
+
+
+# ----------------------------------------------------------------------------- path-test preconditions
+def test_path_case_preconditions():
+    """tests/ref/karto_cases.py builds the inputs of tests/test_karto_paths_gpu.py; each case reaches its kernel
+    path only while its generator keeps a property, asserted here with the oracle alone -- a drifting generator
+    fails here instead of silently no longer reaching the path."""
+    import os
+    import sys
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref"))
+    import karto_cases as K
+
+    # smear sizes: every branch of kt_group (ks <= 15 | > 15) and kt_addscans_kernel (<= 13 | 15 | > 15)
+    for ks, dev in K.SMEAR.items():
+        g = O.karto_grid_info(K.smear_params(ks), K.laser())
+        assert (g["ksize"], g["half"]) == (ks, ks // 2), (dev, g)
+    assert O.karto_grid_info(K.smear_params("loop"), K.laser())["ksize"] == 3
+    assert O.karto_grid_info(K.smear_params(41), K.laser())["half"] > 16  # beyond the 16-cell LDS tile margin
+
+    # ko_count_valid against the plain restatement of FindValidPoints + AddScan's ROI test, on two scans
+    far = K.degenerate()["base_partly_outside"]
+    per = far.count_valid()
+    for b in range(2):
+        pts, valid = K.find_valid_points(far.laser, far.b_ranges[b], far.b_poses[b], far.q_pose[:2])
+        _, inside = K.roi_cells(far, pts)
+        assert per[b] == int((valid & inside).sum()), b
+        if b == 1:  # the base scan 15 m away: partly outside the ROI
+            assert 0 < per[b] < int(valid.sum())
+
+    # dense scan: kt_coarse_kernel's 16-bit flush (504 points per wave; a wave takes a quarter of the points; the
+    # unflushed packed sum of the best pose would pass 65535), kt_prepare_kernel's LDS above 64 KB, kt_fine_kernel's
+    # fourth register round, and every base scan within kt_addscans_kernel's item store (not reached here: the
+    # grid has more than 2048 tiles, but the bound is what keeps its pass loop advancing)
+    dn = K.dense()
+    pts, _ = K.find_valid_points(dn.laser, dn.q_ranges, dn.q_pose, dn.q_pose[:2])
+    npts = len(pts)
+    resp = O.karto_coarse_responses(dn.laser, dn.params, dn.q_ranges, dn.q_pose, dn.b_ranges, dn.b_poses, 16, 21, False)
+    assert npts > 2045 and resp.max() * npts * 25 > 65535, (npts, resp.max())
+    assert dn.laser.n_readings * 24 > 65536 and npts > 3 * 4 * 256
+    assert max(K.footprint_items(dn, b) for b in range(5)) <= K.KT_AS_ITEMS
+
+    # many base scans: more valid points (a lower bound of the footprint items) than one pass of
+    # kt_addscans_kernel holds, for every match whose grid is read; no single base scan overflows it
+    mb = K.many_base_batch()
+    for ks in (13, 41):
+        for i in (0, mb.count // 2, mb.count - 1):
+            c = mb.case(i, K.laser(), K.smear_params(ks))
+            assert int(c.count_valid().sum()) > K.KT_AS_ITEMS, (ks, i)
+            if i == 0:
+                assert max(K.footprint_items(c, b) for b in range(len(c.b_ranges))) <= K.KT_AS_ITEMS
+
+    # expansion that stops late: nothing inside +-20 degrees for the rotated queries, and the pass that answers
+    ex = K.expansion()
+    assert ex[0].match()[2] > 0.5
+    for deg, zero_at, hit_at in ((50, 20, 40), (70, 40, 60), (90, 60, 80)):  # answered by pass 1, 2, 3
+        assert ex[deg].match()[2] > 0.0
+        assert ex[deg].with_params("off", use_response_expansion=0).match()[2] == 0.0
+        at = lambda a: ex[deg].with_params("a", use_response_expansion=0, coarse_search_angle_offset=a * D).match()[2]
+        assert at(zero_at) == 0.0 and at(hit_at) > 0.0, deg
+
+    # headings straddle +-pi; the unnormalised queries are the same headings 3 and 4 turns away
+    hd = K.headings()
+    hs = np.array([c.q_pose[2] for c in hd if abs(c.q_pose[2]) < 4])
+    assert hs.min() < -3.0 and hs.max() > 3.0 and any(c.b_poses[-1, 2] == math.pi for c in hd)
+    assert sum(abs(c.q_pose[2]) > 15 for c in hd) == 2 * len(hs)
+    assert any(c.match()[0][2] < -3.1 for c in hd if c.b_poses[-1, 2] > 3.1)  # a mean across the cut
+
+    # short scans: some chunk of 16 points and some quarter of 4 do not fit the 96 x 96-cell LDS tile of
+    # kt_build_kernel (the quarter and single-point fallbacks)
+    c = K.short(64)[0]
+    h = O.karto_grid_info(c.params, c.laser)["half"]
+    pts, valid = K.find_valid_points(c.laser, c.b_ranges[0], c.b_poses[0], c.q_pose[:2])
+    cells, inside = K.roi_cells(c, pts)
+    ok = valid & inside
+
+    def misfit(size):
+        n = 0
+        for k0 in range(0, len(pts), size):
+            sel = cells[k0:k0 + size][ok[k0:k0 + size]]
+            if len(sel) > 1 and (sel.max(axis=0) - sel.min(axis=0) + 2 * h + 1).max() > 96:
+                n += 1
+        return n
+
+    assert misfit(16) > 0 and misfit(4) > 0
+    assert [len(K.short(n)) for n in K.SHORT_N] == [2] * len(K.SHORT_N)
+    assert K.short(1)[0].count_valid().sum() == 0 and K.short(15)[0].count_valid().sum() > 0
+
+    # degenerate sets
+    dg = K.degenerate()
+    assert not np.any(dg["query_out_of_range"].q_ranges <= 12.0) and dg["query_out_of_range"].count_valid().sum() > 0
+    assert dg["query_out_of_range"].match()[2] == 0.0
+    assert list(dg["empty_base"].count_valid() > 0) == [True, False, True]
+    bh = dg["base_from_behind"]
+    assert int(np.sum(bh.b_ranges[0] <= 12.0)) == 62 and list(bh.count_valid() > 0) == [False, True]
+    front = K.Case("front", bh.laser, bh.params, bh.q_ranges, bh.b_poses[0], bh.b_ranges, bh.b_poses)
+    assert front.count_valid()[0] > 0  # the same patch from its own side is valid
+    mr = dg["minimum_range"]
+    lo = K.Case("lo", K.laser(), mr.params, mr.q_ranges, mr.q_pose, mr.b_ranges, mr.b_poses)
+    assert np.all(mr.count_valid() < lo.count_valid()) and np.all(mr.count_valid() > 0)
+    assert np.sum((mr.q_ranges >= 0.1) & (mr.q_ranges < 3.0)) > 0
+    for name, ties in (("all_tie_21", 441 * 21), ("all_tie_81", 6561 * 21)):
+        c = dg[name]
+        assert len(c.b_ranges) == 0 and ties > 1024  # more than one block round of kt_select_kernel
+        m, cov, r = c.match()
+        assert r == 0.0 and abs(m[0] - c.q_pose[0]) < 1e-9 and abs(m[1] - c.q_pose[1]) < 1e-9

@@ -127,20 +127,39 @@ def test_batch_device_matches_single(gpu):
 
 
 def test_grid_matches_oracle_addscans(gpu):
-    """The device correlation grid after AddScans equals the oracle's byte for byte (grid of the last
-    match is cleared afterwards: a second identical match must give the same result)."""
+    """The device correlation grid after AddScans equals the oracle's byte for byte (kt_copy_grid_device between the
+    two halves of a match), and it is cleared afterwards: all zero, and a second identical match gives the same
+    result."""
+    import torch
+
     lz = _laser()
     p = karto.default_params()
     sm = karto.ScanMatcher(lz, p, max_matches=1, max_scans=16, max_base=10)
     R, T, Q = synth.karto_sequential(1, 10, seed=4)
+    sm.set_scans(0, np.concatenate([R[10:11], R[:10]]), np.concatenate([Q[10:11], T[:10]]))
+    q = torch.zeros(1, dtype=torch.int32, device="cuda")
+    beg = torch.tensor([0, 10], dtype=torch.int32, device="cuda")
+    idx = torch.arange(1, 11, dtype=torch.int32, device="cuda")
+    x = torch.zeros((1, sm.exchange_words()), dtype=torch.int64, device="cuda")
+    res = torch.zeros(C.sizeof(karto.KtResult), dtype=torch.uint8, device="cuda")
+    sm.match_sharded_begin_device(1, q.data_ptr(), beg.data_ptr(), idx.data_ptr(), 0, 1, x.data_ptr())
+    want = O.karto_build_grid(_olaser(lz), _oparams(p), Q[10], R[:10], T[:10])
+    assert want.max() == 100
+    np.testing.assert_array_equal(sm.grid(0), want)
+    sm.match_sharded_end_device(1, beg.data_ptr(), idx.data_ptr(), x.data_ptr(), res.data_ptr())
+    assert not sm.grid(0).any()
+    out = karto.results_from_bytes(res.cpu().numpy())
+    o = O.karto_match(_olaser(lz), _oparams(p), R[10], Q[10], R[:10], T[:10])
+    _same((out["mean"][0], out["covariance"][0].reshape(3, 3), out["response"][0]), o)
     a = sm.MatchScan(R[10], Q[10], R[:10], T[:10])
     b = sm.MatchScan(R[10], Q[10], R[:10], T[:10])
     _same(a, b)
+    _same(a, o)
 
 
 def test_batch_device_loop_window(gpu):
     """A loop-closure candidate batch (>= 128 matches: binned AddScans) on a wide coarse window
-    (21 x 21 positions: the 32 x 32-tile coarse kernel), doPenalize = doRefine = false as
+    (21 x 21 positions: two of the coarse kernel's 16 x 16-position tiles per axis), doPenalize = doRefine = false as
     TryCloseLoop's first call (Mapper.cpp:991-992)."""
     import torch
 
