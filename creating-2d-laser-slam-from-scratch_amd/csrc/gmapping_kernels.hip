@@ -18,7 +18,8 @@
 // 27-207) starts at the endpoint with the smaller major coordinate and, with decision variable
 // d = 2 db - da, steps the minor axis when d >= 0.  In closed form, step i from that start is
 //     (a_s + i, b_s + sb * q(i)),  q(i) = floor((2 db i + da) / (2 da)),  i in [0, da]
-// (checked against the incremental walk on 200k random lines), so every lane clips its line to
+// (checked against the incremental walk on random lines and on 4000-cell lines, in exact integers:
+// tests/ref/gmapping_model.py, tests/test_gmapping_cpu.py), so every lane clips its line to
 // a tile directly.  points[0 .. num_points-2] (all but the end cell p1) get visits++ (:227-234);
 // the end cell of a hit beam gets n++, visits++ and acc += (float)hit (:236-240, map.h:37-48).
 // Counts are order-free integers (LDS atomicAdd on n << 16 | visits); acc is a float sum in beam

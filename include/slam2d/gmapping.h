@@ -54,7 +54,11 @@ int gm_get_map_size(gm_ctx *ctx, int *size_x, int *size_y);
 
 /* ComputeMap of one scan for particles [0, P): poses double[4*P] (host), ranges float[n] (host,
  * n <= max_beams, the LaserScan ranges), synchronous.  Before overwriting, every particle scores the
- * scan against its previous map (build-defined weight, see gm_get_scores). */
+ * scan against its previous map (build-defined weight, see gm_get_scores).
+ * Ranges as in the reference: only d > maxRange, d == 0 and non-finite d are dropped, so a negative range is a
+ * valid beam (a hit, drawn backwards).  A beam whose end cell lies 16384 or more cells from the pose's cell in x or
+ * y is not representable and is dropped from the map; within the limits of gm_create only a negative range below
+ * -max_range can do that.  Such a beam is still counted in `hits` (gm_get_scores). */
 int gm_compute_maps(gm_ctx *ctx, const double *poses, const float *ranges, int n);
 /* Device-pointer form for particles [particle_begin, particle_begin + count): d_poses double[4*count],
  * d_ranges float[n], d_scores_out int32[count] or NULL; stream-ordered on hip_stream (NULL = own). */

@@ -100,8 +100,10 @@ long long gmo_compute_map(double px, double py, double ct, double st, const floa
     if (acc_out) memset(acc_out, 0, sizeof(float) * 2 * (size_t)sx * sy);
     int p0x, p0y;
     gmo_world2map(px, py, cx, cy, delta, sx2, sy2, &p0x, &p0y);
-    int cap = 2 * (sx + sy + 8);
-    int *pts = (int *)malloc(sizeof(int) * 2 * (size_t)cap);
+    /* one point buffer, grown to each line's max(|dx|, |dy|) + 1 points: a beam is up to max_range / delta cells
+     * long whatever the map size (a 96 x 64-cell map and one 20 m beam overran a buffer sized from the map) */
+    size_t cap = 0;
+    int *pts = NULL;
     long long nfree = 0;
     int nh = 0, bad = 0;
     /* free pass (all lines first, then hits: gmapping.cc:227-241) */
@@ -119,6 +121,13 @@ long long gmo_compute_map(double px, double py, double ct, double st, const floa
         wy += d * diry;
         int p1x, p1y;
         gmo_world2map(wx, wy, cx, cy, delta, sx2, sy2, &p1x, &p1y);
+        long long ddx = llabs((long long)p1x - p0x), ddy = llabs((long long)p1y - p0y);
+        size_t need = (size_t)(ddx > ddy ? ddx : ddy) + 1;
+        if (need > cap) {
+            free(pts);
+            cap = need;
+            pts = (int *)malloc(sizeof(int) * 2 * cap);
+        }
         int np = gmo_grid_line(p0x, p0y, p1x, p1y, pts);
         for (int k = 0; k < np - 1; k++) {
             int x = pts[2 * k], y = pts[2 * k + 1];

@@ -1,8 +1,8 @@
 """GPU parity of the GMapping particle-map path (config 4): gm_compute_kernel through the C-ABI vs
 the GMapping oracle (itself pinned bit-for-bit to the reference's own grid headers,
 tests/test_gmapping_cpu.py).  Counts (n, visits) and the float hit accumulators are bit-exact."""
-import math
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -10,6 +10,9 @@ import pytest
 import oracle as O
 from slam2d import synth
 from slam2d.gmapping import GMappingFleet
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref"))
+import gmapping_cases as G  # noqa: E402  (expected_score and C round() live with the case builder)
 
 pytestmark = pytest.mark.gpu
 
@@ -22,44 +25,6 @@ def _oracle_maps(poses4, ranges, ang):
         n, v, acc, nfree, nh = O.gm_compute(ranges, np.cos(ang), np.sin(ang), tuple(p))
         out.append((n, v, acc, nfree, nh))
     return out
-
-
-def _cround(x):
-    """C round(): half away from zero."""
-    f = math.floor(x)
-    d = x - f
-    if d > 0.5 or (d == 0.5 and x > 0):
-        return f + 1
-    return f
-
-
-def _expected_score(prev, pose4, ranges, ang, p=O.GM_DEFAULTS, thresh=0.25):
-    """Hit beams whose end cell is occupied (n/visits > thresh) in the previous map."""
-    if prev is None:
-        return 0
-    n_prev, v_prev = prev
-    sx, sy, sx2, sy2 = O.gm_geometry(p)
-    cx, cy = (p["xmin"] + p["xmax"]) / 2.0, (p["ymin"] + p["ymax"]) / 2.0
-    px, py, ct, st = (float(v) for v in pose4)
-    score = 0
-    for i, r in enumerate(ranges.astype(np.float64)):
-        d = float(r)
-        if d > p["max_range"] or d == 0.0 or not math.isfinite(d):
-            continue
-        if d > p["max_urange"]:
-            d = p["max_urange"]
-        if not d < p["max_urange"]:
-            continue
-        ca, sa = math.cos(ang[i]), math.sin(ang[i])
-        dirx = ct * ca - st * sa
-        diry = st * ca + ct * sa
-        wx = px + d * dirx
-        wy = py + d * diry
-        x = _cround((wx - cx) / p["delta"]) + sx2
-        y = _cround((wy - cy) / p["delta"]) + sy2
-        if 0 <= x < sx and 0 <= y < sy and v_prev[y, x] > 0 and n_prev[y, x] / v_prev[y, x] > thresh:
-            score += 1
-    return score
 
 
 def _check_maps(fleet, ref, P):
@@ -119,7 +84,7 @@ def test_particles_scores_and_fresh_maps(gpu):
         _check_maps(fleet, ref, P)
         s, h, f = fleet.scores()
         for p in range(P):
-            assert s[p] == _expected_score(prev[p], poses4[p], ranges, ang), (t, p)
+            assert s[p] == G.expected_score(prev[p], poses4[p], ranges, np.cos(ang), np.sin(ang)), (t, p)
             assert h[p] == ref[p][4] and f[p] == ref[p][3], (t, p)
             prev[p] = (ref[p][0], ref[p][1])
         if t:
