@@ -883,6 +883,18 @@ int hs_get_last_pose(hs_ctx *c, int stream, float pose_out[3], float cov_out[9])
     return HS_OK;
 }
 
+int hs_get_clamp_count(hs_ctx *c, int stream, int *out)
+{
+    if (check_stream(c, stream) != HS_OK || !out) return fail(HS_EINVAL, "bad ctx/stream/pointer");
+    LOCK(c);
+    if (dev_enter(c, c->stream) != HS_OK) return HS_EHIP;
+    StreamState st;
+    HCHK(hipMemcpyAsync(&st, c->d_state + stream, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+    HCHK(hipStreamSynchronize(c->stream));
+    *out = st.clamp_count;
+    return HS_OK;
+}
+
 int hs_get_map(hs_ctx *c, int stream, int level, int8_t *occ_out, float *logodds_out, int32_t *upd_out,
                int *update_index_out)
 {

@@ -49,6 +49,7 @@ def _declare(L):
     L.hs_match.argtypes = [_p, _i, _p, _i, _f, _f, _p, _p, _p]
     L.hs_update_by_scan.argtypes = [_p, _i, _p, _i, _f, _f, _p]
     L.hs_get_last_pose.argtypes = [_p, _i, _p, _p]
+    L.hs_get_clamp_count.argtypes = [_p, _i, P(_i)]
     L.hs_get_map.argtypes = [_p, _i, _i, _p, _p, _p, P(_i)]
     L.hs_set_map.argtypes = [_p, _i, _i, _p, _p]
     L.hs_step_batch_device.argtypes = [_p, _i, _i, _p, _i, _p, _p, _p, _p]

@@ -182,6 +182,12 @@ class HectorFleet:
         check(self.L.hs_get_last_pose(self.h, stream, _fp(pose), _fp(cov)), "hs_get_last_pose")
         return pose, cov.reshape(3, 3)
 
+    def clamp_count(self, stream: int = 0) -> int:
+        """Gauss-Newton steps of the stream whose rotation update was cut to +-0.2 rad (hs_get_clamp_count)."""
+        n = C.c_int()
+        check(self.L.hs_get_clamp_count(self.h, stream, C.byref(n)), "hs_get_clamp_count")
+        return n.value
+
     def map_info(self, level: int = 0):
         sx, sy, cl = C.c_int(), C.c_int(), C.c_float()
         org = np.zeros(2, np.float32)

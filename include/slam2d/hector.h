@@ -93,6 +93,10 @@ int hs_update_by_scan(hs_ctx *ctx, int stream, const float *xy, int n, float ox,
 
 /* HectorSlamProcessor::getLastScanMatchPose / getLastScanMatchCovariance (HectorSlamProcessor.h:120-122) */
 int hs_get_last_pose(hs_ctx *ctx, int stream, float pose_out[3], float cov_out[9]);
+/* Gauss-Newton steps of the stream, since hs_create, whose rotation update was cut to +-0.2 rad: the events
+ * the reference reports as "SearchDir angle change too large" (ScanMatcher.h:123-132).  hs_reset keeps the
+ * count.  A host-side copy of the stream's state (synchronises); no reference counterpart. */
+int hs_get_clamp_count(hs_ctx *ctx, int stream, int *count_out);
 
 /* getGridMap(level) read-out (MapRepresentationInterface.h:54) in the publishMap format
  * (hector_slam.cc:287-304): occ_out int8 row-major (-1 unknown, 0 free, 100 occupied); optional raw
@@ -100,7 +104,9 @@ int hs_get_last_pose(hs_ctx *ctx, int stream, float pose_out[3], float cov_out[9
  * Any output pointer may be NULL. */
 int hs_get_map(hs_ctx *ctx, int stream, int level, int8_t *occ_out, float *logodds_out, int32_t *cell_update_index_out,
                int *update_index_out);
-/* Overwrite one level's cells (log-odds + updateIndex); for tests and map reload. */
+/* Overwrite one level's cells (log-odds + updateIndex); for tests and map reload.  The indices must not lie ahead of
+ * the stream's own update index (3 per grid update since hs_create, GridMapBase.h:334), as none does in a map the
+ * reference or this library wrote at that index; a map reloaded into a fresh context passes -1 (never updated). */
 int hs_set_map(hs_ctx *ctx, int stream, int level, const float *logodds, const int32_t *cell_update_index);
 
 /* ---- batched, device-resident throughput path ------------------------------------------------ */

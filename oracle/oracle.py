@@ -202,6 +202,10 @@ class HectorOracle:
     def valid_rays(self):
         return int(self.L.ho_valid_rays(self.h))
 
+    def clamp_count(self):
+        """Gauss-Newton steps so far whose rotation update was cut to +-0.2 rad (ScanMatcher.h:123-132)."""
+        return int(self.L.ho_clamp_count(self.h))
+
     def factors(self):
         a, b = _f(), _f()
         self.L.ho_get_factors(self.h, C.byref(a), C.byref(b))

@@ -168,13 +168,20 @@ def test_maprep_hip_compiles_against_reference_headers():
     assert bad.returncode != 0 and "override" in bad.stderr, bad.stderr
 
 
-def test_cpp_test_host_links_the_product_library():
-    """tests/cpp/build/hector_threads_test (built by build()) resolves libslam2d.so from the tree."""
+def test_cpp_test_host_links_the_product_library(libpath):
+    """tests/cpp/build/hector_threads_test (built by build(); built here where it is missing, never skipped) resolves
+    libslam2d.so from the tree: the path the loader reports is the tree's own library, whatever links the checkout
+    is reached through."""
     b = os.path.join(REPO, "tests", "cpp", "build", "hector_threads_test")
     if not os.path.exists(b):
-        pytest.skip("tests/cpp not built")
-    out = subprocess.run(["ldd", b], capture_output=True, text=True).stdout
-    assert "libslam2d.so => " + REPO in out.replace("tests/cpp/build/../../../", ""), out
+        subprocess.run(["make", "-s", "-C", os.path.join(REPO, "tests", "cpp"), "build/hector_threads_test"],
+                       capture_output=True, text=True, check=True)
+    r = subprocess.run(["ldd", b], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    found = re.findall(r"^\s*libslam2d\.so => (\S+)", r.stdout, flags=re.M)
+    assert len(found) == 1, r.stdout
+    assert os.path.realpath(found[0]) == os.path.realpath(libpath), (found, libpath)
+    assert os.path.realpath(libpath).startswith(os.path.realpath(REPO) + os.sep), libpath
 
 
 def test_library_source_id_matches_tree():
