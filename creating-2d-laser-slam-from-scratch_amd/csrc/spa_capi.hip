@@ -1,0 +1,395 @@
+// spa_capi.hip -- host runtime + extern "C" boundary (include/slam2d/spa.h) of the pose-graph optimiser.
+// The optimisation runs in spa_kernels.hip; the host keeps each graph's nodes and constraints (spa_graph.h) and
+// uploads an edited graph before its next compute.  Without a usable HIP device spa_create fails with SPA_ENODEV
+// (no CPU fallback).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "spa_graph.h"
+#include "spa_kernels.hip"
+
+using namespace s2d;
+
+namespace {
+thread_local std::string spa_err;
+
+int sfail(int code, const char *what, hipError_t e = hipSuccess)
+{
+    spa_err = what;
+    if (e != hipSuccess) {
+        spa_err += ": ";
+        spa_err += hipGetErrorString(e);
+    }
+    return code;
+}
+
+#define SCHK(expr)                                               \
+    do {                                                         \
+        hipError_t _e = (expr);                                  \
+        if (_e != hipSuccess) return sfail(SPA_EHIP, #expr, _e); \
+    } while (0)
+
+constexpr int SPA_MAX_GRAPHS = 1 << 16;
+constexpr int SPA_MAX_NODES = 1 << 20;
+constexpr int SPA_MAX_CONS = 1 << 22;
+}  // namespace
+
+struct spa_ctx {
+    int G = 0, N = 0, M = 0;
+    std::vector<SpaGraph> graphs;
+    std::vector<int> uploaded_nodes;  // per graph: nodes [0, uploaded) have their pose on the device
+    std::vector<char> dirty;          // per graph: edited since the last upload
+    std::vector<int> n_fixed;         // per graph: SysSPA2d::nFixed, or SPA_FIXED_FROM_PARAMS
+    SpaDev dev{};
+    SpaHdr *d_hdr = nullptr;
+    int2 *d_con_nd = nullptr, *d_nbr = nullptr;
+    double *d_con_mean = nullptr, *d_con_prec = nullptr;
+    int *d_inc_off = nullptr, *d_inc = nullptr, *d_nbr_off = nullptr, *d_pair_off = nullptr, *d_pair_con = nullptr;
+    size_t scratch_bytes = 0;
+    hipStream_t stream = nullptr, last = nullptr;
+    hipEvent_t ev_last = nullptr;
+    std::mutex mu;
+};
+
+namespace {
+
+int check_graph(const spa_ctx *c, int g)
+{
+    if (!c) return sfail(SPA_EINVAL, "ctx is NULL");
+    if (g < 0 || g >= c->G) return sfail(SPA_EINVAL, "graph index out of range");
+    return SPA_OK;
+}
+
+int wait_last(spa_ctx *c)
+{
+    if (c->last) SCHK(hipStreamSynchronize(c->last));
+    return SPA_OK;
+}
+
+// An edited graph: its index lists, constraints and the poses of the nodes added since the last upload.  The
+// copies are synchronous and follow the context's previous device work.
+int upload_graph(spa_ctx *c, int g)
+{
+    SpaGraph &gr = c->graphs[g];
+    int rc = wait_last(c);
+    if (rc != SPA_OK) return rc;
+    gr.compile();
+    const size_t N = (size_t)c->N, M = (size_t)c->M;
+    const int n = gr.n_nodes(), m = gr.n_cons();
+    const SpaHdr h{n, m, gr.n_pairs(), c->n_fixed[g]};
+    SCHK(hipMemcpy(c->d_hdr + g, &h, sizeof(h), hipMemcpyHostToDevice));
+    const int up = c->uploaded_nodes[g];
+    if (n > up)
+        SCHK(hipMemcpy(c->dev.poses + (g * N + up) * 3, gr.poses.data() + (size_t)up * 3, sizeof(double) * 3 * (n - up),
+                       hipMemcpyHostToDevice));
+    c->uploaded_nodes[g] = n;
+    if (m > 0) {
+        SCHK(hipMemcpy(c->d_con_nd + g * M, gr.ends.data(), sizeof(int) * 2 * m, hipMemcpyHostToDevice));
+        SCHK(hipMemcpy(c->d_con_mean + g * M * 3, gr.means.data(), sizeof(double) * 3 * m, hipMemcpyHostToDevice));
+        SCHK(hipMemcpy(c->d_con_prec + g * M * 9, gr.precs.data(), sizeof(double) * 9 * m, hipMemcpyHostToDevice));
+        SCHK(hipMemcpy(c->d_inc + g * 2 * M, gr.inc.data(), sizeof(int) * gr.inc.size(), hipMemcpyHostToDevice));
+        SCHK(hipMemcpy(c->d_pair_con + g * M, gr.pair_con.data(), sizeof(int) * m, hipMemcpyHostToDevice));
+        if (!gr.nbr.empty())
+            SCHK(hipMemcpy(c->d_nbr + g * 2 * M, gr.nbr.data(), sizeof(int) * 2 * gr.nbr.size(), hipMemcpyHostToDevice));
+    }
+    SCHK(hipMemcpy(c->d_inc_off + g * (N + 1), gr.inc_off.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice));
+    SCHK(hipMemcpy(c->d_nbr_off + g * (N + 1), gr.nbr_off.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice));
+    SCHK(hipMemcpy(c->d_pair_off + g * (M + 1), gr.pair_off.data(), sizeof(int) * gr.pair_off.size(),
+                   hipMemcpyHostToDevice));
+    c->dirty[g] = 0;
+    return SPA_OK;
+}
+
+int check_params(const spa_params *p)
+{
+    if (!p) return sfail(SPA_EINVAL, "params is NULL");
+    if (p->niter < 0 || p->niter > SPA_MAX_NITER) return sfail(SPA_EINVAL, "niter must be in [0, SPA_MAX_NITER]");
+    if (p->max_cg_iters < 0 || p->max_cg_iters > SPA_MAX_CG_ITERS)
+        return sfail(SPA_EINVAL, "max_cg_iters must be in [0, SPA_MAX_CG_ITERS]");
+    if ((long long)p->niter * p->max_cg_iters > SPA_MAX_ITER_PRODUCT)
+        return sfail(SPA_EINVAL, "niter * max_cg_iters exceeds SPA_MAX_ITER_PRODUCT");
+    if (!(p->lambda > 0) || !std::isfinite(p->lambda)) return sfail(SPA_EINVAL, "lambda must be > 0 and finite");
+    if (!(p->init_tol >= 0)) return sfail(SPA_EINVAL, "init_tol must be >= 0");
+    return SPA_OK;
+}
+
+int run(spa_ctx *c, int g_first, int count, const spa_params *p, hipStream_t s)
+{
+    int rc = check_params(p);
+    if (rc != SPA_OK) return rc;
+    if (g_first < 0 || count < 0 || g_first > c->G - count) return sfail(SPA_EINVAL, "graph range out of bounds");
+    if (count == 0) return SPA_OK;
+    for (int g = g_first; g < g_first + count; ++g)
+        if (c->dirty[g] && (rc = upload_graph(c, g)) != SPA_OK) return rc;
+    // order after the context's previous device work, whichever stream it ran on (DESIGN.md "Streams")
+    SCHK(hipStreamWaitEvent(s, c->ev_last, 0));
+    hipLaunchKernelGGL(spa_solve_kernel, dim3((unsigned)count), dim3(SPA_THREADS), 0, s, c->dev, g_first, *p);
+    SCHK(hipGetLastError());
+    SCHK(hipEventRecord(c->ev_last, s));
+    c->last = s;
+    return SPA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *spa_last_error(void) { return spa_err.c_str(); }
+const char *spa_version(void) { return "slam2d-spa 1 (gfx950, block-Jacobi PCG)"; }
+
+void spa_default_params(spa_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->niter = 40;          // spa_solver.cc:51
+    p->max_cg_iters = 50;   // spa2d.h:249
+    p->n_fixed = 1;         // spa2d.h:198
+    p->lambda = 1.0e-4;     // spa2d.h:249
+    p->init_tol = 1.0e-8;   // spa2d.h:249
+}
+
+int spa_create(spa_ctx **out, int max_graphs, int max_nodes, int max_constraints)
+{
+    if (!out) return sfail(SPA_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (max_graphs < 1 || max_graphs > SPA_MAX_GRAPHS || max_nodes < 1 || max_nodes > SPA_MAX_NODES ||
+        max_constraints < 1 || max_constraints > SPA_MAX_CONS)
+        return sfail(SPA_EINVAL, "need 1 <= max_graphs <= 2^16, 1 <= max_nodes <= 2^20, 1 <= max_constraints <= 2^22");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return sfail(SPA_ENODEV, "no HIP device");
+    spa_ctx *c = new spa_ctx;
+    c->G = max_graphs;
+    c->N = max_nodes;
+    c->M = max_constraints;
+    c->graphs.resize((size_t)max_graphs);
+    c->uploaded_nodes.assign((size_t)max_graphs, 0);
+    c->dirty.assign((size_t)max_graphs, 1);
+    c->n_fixed.assign((size_t)max_graphs, SPA_FIXED_FROM_PARAMS);
+    const size_t G = (size_t)max_graphs, N = (size_t)max_nodes, M = (size_t)max_constraints;
+    c->scratch_bytes = sizeof(double) * G * spa_scratch_doubles(max_nodes, max_constraints);
+    hipError_t e;
+    if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamDefault)) != hipSuccess ||
+        (e = hipEventCreateWithFlags(&c->ev_last, hipEventDisableTiming)) != hipSuccess) {
+        spa_destroy(c);
+        return sfail(SPA_EHIP, "hipStreamCreate", e);
+    }
+    if ((e = hipMalloc(&c->d_hdr, sizeof(SpaHdr) * G)) != hipSuccess ||
+        (e = hipMalloc(&c->dev.poses, sizeof(double) * G * N * 3)) != hipSuccess ||
+        (e = hipMalloc(&c->d_con_nd, sizeof(int2) * G * M)) != hipSuccess ||
+        (e = hipMalloc(&c->d_con_mean, sizeof(double) * G * M * 3)) != hipSuccess ||
+        (e = hipMalloc(&c->d_con_prec, sizeof(double) * G * M * 9)) != hipSuccess ||
+        (e = hipMalloc(&c->d_inc_off, sizeof(int) * G * (N + 1))) != hipSuccess ||
+        (e = hipMalloc(&c->d_inc, sizeof(int) * G * 2 * M)) != hipSuccess ||
+        (e = hipMalloc(&c->d_nbr_off, sizeof(int) * G * (N + 1))) != hipSuccess ||
+        (e = hipMalloc(&c->d_nbr, sizeof(int2) * G * 2 * M)) != hipSuccess ||
+        (e = hipMalloc(&c->d_pair_off, sizeof(int) * G * (M + 1))) != hipSuccess ||
+        (e = hipMalloc(&c->d_pair_con, sizeof(int) * G * M)) != hipSuccess ||
+        (e = hipMalloc(&c->dev.scratch, c->scratch_bytes)) != hipSuccess ||
+        (e = hipMalloc(&c->dev.stats, sizeof(spa_stats) * G)) != hipSuccess) {
+        spa_destroy(c);
+        return sfail(SPA_ENOMEM, "hipMalloc", e);
+    }
+    c->dev.max_nodes = max_nodes;
+    c->dev.max_cons = max_constraints;
+    c->dev.hdr = c->d_hdr;
+    c->dev.con_nd = c->d_con_nd;
+    c->dev.con_mean = c->d_con_mean;
+    c->dev.con_prec = c->d_con_prec;
+    c->dev.inc_off = c->d_inc_off;
+    c->dev.inc = c->d_inc;
+    c->dev.nbr_off = c->d_nbr_off;
+    c->dev.nbr = c->d_nbr;
+    c->dev.pair_off = c->d_pair_off;
+    c->dev.pair_con = c->d_pair_con;
+    std::vector<spa_stats> st(G);
+    for (auto &x : st) {
+        memset(&x, 0, sizeof(x));
+        x.status = SPA_NOT_RUN;
+    }
+    if ((e = hipMemcpy(c->dev.stats, st.data(), sizeof(spa_stats) * G, hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemset(c->dev.poses, 0, sizeof(double) * G * N * 3)) != hipSuccess ||
+        (e = hipEventRecord(c->ev_last, c->stream)) != hipSuccess) {
+        spa_destroy(c);
+        return sfail(SPA_EHIP, "initialising the context", e);
+    }
+    *out = c;
+    return SPA_OK;
+}
+
+int spa_destroy(spa_ctx *c)
+{
+    if (!c) return SPA_OK;
+    if (c->last) hipStreamSynchronize(c->last);
+    if (c->stream) hipStreamSynchronize(c->stream);
+    void *bufs[] = {c->d_hdr, c->dev.poses, c->d_con_nd, c->d_con_mean, c->d_con_prec, c->d_inc_off, c->d_inc,
+                    c->d_nbr_off, c->d_nbr, c->d_pair_off, c->d_pair_con, c->dev.scratch, c->dev.stats};
+    for (void *b : bufs)
+        if (b) hipFree(b);
+    if (c->ev_last) hipEventDestroy(c->ev_last);
+    if (c->stream) hipStreamDestroy(c->stream);
+    delete c;
+    return SPA_OK;
+}
+
+int spa_add_node(spa_ctx *c, int g, int id, const double *pose)
+{
+    int rc = check_graph(c, g);
+    if (rc != SPA_OK) return rc;
+    if (!pose) return sfail(SPA_EINVAL, "pose is NULL");
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (c->graphs[g].n_nodes() >= c->N) return sfail(SPA_ERANGE, "the graph already has max_nodes nodes");
+    c->graphs[g].add_node(id, pose);
+    c->dirty[g] = 1;
+    return SPA_OK;
+}
+
+int spa_add_constraint(spa_ctx *c, int g, int id0, int id1, const double *mean, const double *prec, int *added)
+{
+    if (added) *added = 0;
+    int rc = check_graph(c, g);
+    if (rc != SPA_OK) return rc;
+    if (!mean || !prec) return sfail(SPA_EINVAL, "NULL argument");
+    if (id0 == id1) return sfail(SPA_EINVAL, "a constraint from a node to itself");
+    std::lock_guard<std::mutex> lock(c->mu);
+    SpaGraph &gr = c->graphs[g];
+    const int ni0 = gr.find(id0), ni1 = gr.find(id1);
+    if (ni0 < 0 || ni1 < 0) return SPA_OK;  // addConstraint returns false (:241)
+    if (ni0 == ni1) return sfail(SPA_EINVAL, "a constraint from a node to itself");
+    if (gr.n_cons() >= c->M) return sfail(SPA_ERANGE, "the graph already has max_constraints constraints");
+    gr.add_constraint_by_index(ni0, ni1, mean, prec);
+    c->dirty[g] = 1;
+    if (added) *added = 1;
+    return SPA_OK;
+}
+
+int spa_set_graph(spa_ctx *c, int g, int n_nodes, const int *ids, const double *poses, int n_cons, const int *ends,
+                  const double *means, const double *precs)
+{
+    int rc = check_graph(c, g);
+    if (rc != SPA_OK) return rc;
+    if (n_nodes < 0 || n_cons < 0) return sfail(SPA_EINVAL, "negative count");
+    if (n_nodes > c->N || n_cons > c->M) return sfail(SPA_ERANGE, "more nodes or constraints than the context holds");
+    if ((n_nodes > 0 && (!ids || !poses)) || (n_cons > 0 && (!ends || !means || !precs)))
+        return sfail(SPA_EINVAL, "NULL argument");
+    for (int ci = 0; ci < n_cons; ++ci) {
+        const int a = ends[2 * ci], b = ends[2 * ci + 1];
+        if (a < 0 || a >= n_nodes || b < 0 || b >= n_nodes) return sfail(SPA_EINVAL, "constraint end out of range");
+        if (a == b) return sfail(SPA_EINVAL, "a constraint from a node to itself");
+    }
+    std::lock_guard<std::mutex> lock(c->mu);
+    SpaGraph &gr = c->graphs[g];
+    gr.clear();
+    for (int k = 0; k < n_nodes; ++k) gr.add_node(ids[k], poses + 3 * k);
+    for (int ci = 0; ci < n_cons; ++ci) gr.add_constraint_by_index(ends[2 * ci], ends[2 * ci + 1], means + 3 * ci, precs + 9 * ci);
+    c->uploaded_nodes[g] = 0;
+    c->dirty[g] = 1;
+    return SPA_OK;
+}
+
+int spa_clear_graph(spa_ctx *c, int g)
+{
+    int rc = check_graph(c, g);
+    if (rc != SPA_OK) return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    c->graphs[g].clear();
+    c->uploaded_nodes[g] = 0;
+    c->dirty[g] = 1;
+    return SPA_OK;
+}
+
+int spa_set_n_fixed(spa_ctx *c, int g, int n_fixed)
+{
+    int rc = check_graph(c, g);
+    if (rc != SPA_OK) return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    c->n_fixed[g] = n_fixed;
+    c->dirty[g] = 1;
+    return SPA_OK;
+}
+
+int spa_get_counts(spa_ctx *c, int g, int *n_nodes, int *n_cons)
+{
+    int rc = check_graph(c, g);
+    if (rc != SPA_OK) return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (n_nodes) *n_nodes = c->graphs[g].n_nodes();
+    if (n_cons) *n_cons = c->graphs[g].n_cons();
+    return SPA_OK;
+}
+
+int spa_compute_device(spa_ctx *c, int g_first, int count, const spa_params *params, void *hip_stream)
+{
+    if (!c) return sfail(SPA_EINVAL, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(c->mu);
+    return run(c, g_first, count, params, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
+int spa_compute(spa_ctx *c, int g_first, int count, const spa_params *params)
+{
+    if (!c) return sfail(SPA_EINVAL, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(c->mu);
+    int rc = run(c, g_first, count, params, c->stream);
+    if (rc != SPA_OK) return rc;
+    SCHK(hipStreamSynchronize(c->stream));
+    return SPA_OK;
+}
+
+int spa_get_nodes(spa_ctx *c, int g, int *ids_out, double *poses_out)
+{
+    int rc = check_graph(c, g);
+    if (rc != SPA_OK) return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if ((rc = wait_last(c)) != SPA_OK) return rc;
+    const SpaGraph &gr = c->graphs[g];
+    const int n = gr.n_nodes(), up = c->uploaded_nodes[g];
+    if (ids_out)
+        for (int k = 0; k < n; ++k) ids_out[k] = gr.ids[k];
+    if (poses_out) {
+        if (up > 0)
+            SCHK(hipMemcpy(poses_out, c->dev.poses + (size_t)g * c->N * 3, sizeof(double) * 3 * up, hipMemcpyDeviceToHost));
+        for (int k = up; k < n; ++k)
+            for (int q = 0; q < 3; ++q) poses_out[3 * k + q] = gr.poses[(size_t)3 * k + q];
+    }
+    return SPA_OK;
+}
+
+int spa_device_poses(spa_ctx *c, int g, const double **d_poses, int *n)
+{
+    int rc = check_graph(c, g);
+    if (rc != SPA_OK) return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (c->dirty[g] && (rc = upload_graph(c, g)) != SPA_OK) return rc;  // nodes added since the last compute
+    if (d_poses) *d_poses = c->dev.poses + (size_t)g * c->N * 3;
+    if (n) *n = c->graphs[g].n_nodes();
+    return SPA_OK;
+}
+
+int spa_get_stats(spa_ctx *c, int g, spa_stats *stats)
+{
+    int rc = check_graph(c, g);
+    if (rc != SPA_OK) return rc;
+    if (!stats) return sfail(SPA_EINVAL, "stats is NULL");
+    std::lock_guard<std::mutex> lock(c->mu);
+    if ((rc = wait_last(c)) != SPA_OK) return rc;
+    SCHK(hipMemcpy(stats, c->dev.stats + g, sizeof(*stats), hipMemcpyDeviceToHost));
+    return SPA_OK;
+}
+
+int spa_poison_scratch(spa_ctx *c, int byte)
+{
+    if (!c) return sfail(SPA_EINVAL, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(c->mu);
+    int rc = wait_last(c);
+    if (rc != SPA_OK) return rc;
+    SCHK(hipMemset(c->dev.scratch, byte, c->scratch_bytes));
+    SCHK(hipDeviceSynchronize());
+    return SPA_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,421 @@
+// spa_kernels.hip -- Karto's pose-graph optimiser on the device: SysSPA2d::doSPA in its block-Jacobi PCG mode
+// (lesson6/lib/sparse_bundle_adjustment/src/spa2d.cpp:425-609 with useCSparse = SBA_BLOCK_JACOBIAN_PCG).
+//
+// One 256-thread workgroup per graph runs the whole LM loop, PCG loops inside, in one launch: no grid-wide
+// synchronisation, no cooperative launch, nothing waits on another workgroup.  A graph's working arrays live in
+// its slice of the context's scratch (global memory, L2-resident at these sizes); LDS holds the 256 reduction
+// lanes and the broadcast header.  Every value a barrier-enclosing branch or loop tests (dn < d0, sqDiff <
+// sqMinDelta, newcost < cost, the iteration bounds, the graph's status) is the same on all lanes: it is read
+// from LDS (the reduction's lane 0, the header) or computed from such values by the same operations.  NaN makes
+// the comparisons false on every lane alike, so the loops end at their bounds.
+//
+// Arithmetic: IEEE double, -ffp-contract=off, in the orders include/slam2d/spa.h states; tests/ref/spa2d_ref.c
+// restates the same sequence with the reference's scatter loops, and the two agree bit for bit.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include "../../include/slam2d/spa.h"
+#include "detmath.h"
+
+namespace s2d {
+
+constexpr int SPA_THREADS = SPA_REDUCE_LANES;
+constexpr int SPA_CON_DOUBLES = 33;  // per constraint: J0'KJ0 [9], J1'(KJ1) [9], the off-diagonal block [9], J0'Ke [3], J1'Ke [3]
+// doubles of scratch per node / per constraint (spa_scratch_doubles)
+constexpr int SPA_NODE_DOUBLES = 6 + 9 + 9 + 3 * 7;   // w2n, diag, inverse, B x r d q s, saved pose
+constexpr int SPA_CONS_DOUBLES = SPA_CON_DOUBLES + 9;  // products, pair block
+
+struct SpaHdr {
+    int n_nodes, n_cons, n_pairs;
+    int n_fixed;  // SysSPA2d::nFixed of this graph, or SPA_FIXED_FROM_PARAMS
+};
+
+// The context's device arrays; graph g owns [g * max_nodes, ...) / [g * max_cons, ...) of each.
+struct SpaDev {
+    int max_nodes, max_cons;
+    const SpaHdr *hdr;        // [G]
+    double *poses;            // [G][N][3]: x, y, heading -- persistent
+    const int2 *con_nd;       // [G][M]: ndr, nd1 (node indices)
+    const double *con_mean;   // [G][M][3]
+    const double *con_prec;   // [G][M][9]
+    const int *inc_off;       // [G][N + 1]: per node, its incident constraints in constraint order
+    const int *inc;           // [G][2M]: constraint * 2 + end (0: the node is ndr, 1: it is nd1)
+    const int *nbr_off;       // [G][N + 1]: per node, its off-diagonal neighbours in ascending node index
+    const int2 *nbr;          // [G][2M]: neighbour node, pair
+    const int *pair_off;      // [G][M + 1]: per unordered node pair, its constraints in constraint order
+    const int *pair_con;      // [G][M]
+    double *scratch;          // [G][spa_scratch_doubles]
+    spa_stats *stats;         // [G]
+};
+
+__host__ __device__ inline size_t spa_scratch_doubles(int max_nodes, int max_cons)
+{
+    return (size_t)max_nodes * SPA_NODE_DOUBLES + (size_t)max_cons * SPA_CONS_DOUBLES;
+}
+
+// C = A * B, each element (a0*b0 + a1*b1) + a2*b2
+__device__ inline void spa_mul33(const double *A, const double *B, double *C)
+{
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) C[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
+}
+__device__ inline void spa_mv3(const double *A, const double *v, double *o)
+{
+    for (int i = 0; i < 3; ++i) o[i] = (A[3 * i] * v[0] + A[3 * i + 1] * v[1]) + A[3 * i + 2] * v[2];
+}
+// o = A' * v
+__device__ inline void spa_mtv3(const double *A, const double *v, double *o)
+{
+    for (int j = 0; j < 3; ++j) o[j] = (A[j] * v[0] + A[3 + j] * v[1]) + A[6 + j] * v[2];
+}
+__device__ inline void spa_tr33(const double *A, double *T)
+{
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) T[3 * i + j] = A[3 * j + i];
+}
+__device__ inline double spa_dot3(const double *a, const double *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+
+// Matrix3d::inverse (bpcg.h:282), order fixed here: cofactors divided by det = (a*c00 + b*c10) + c*c20
+__device__ inline void spa_inv33(const double *m, double *o)
+{
+    const double a = m[0], b = m[1], c = m[2], d = m[3], e = m[4], f = m[5], g = m[6], h = m[7], i = m[8];
+    const double c00 = e * i - f * h, c01 = c * h - b * i, c02 = b * f - c * e;
+    const double c10 = f * g - d * i, c11 = a * i - c * g, c12 = c * d - a * f;
+    const double c20 = d * h - e * g, c21 = b * g - a * h, c22 = a * e - b * d;
+    const double det = (a * c00 + b * c10) + c * c20;
+    o[0] = c00 / det; o[1] = c01 / det; o[2] = c02 / det;
+    o[3] = c10 / det; o[4] = c11 / det; o[5] = c12 / det;
+    o[6] = c20 / det; o[7] = c21 / det; o[8] = c22 / det;
+}
+
+// Node2d::setTransform (spa2d.cpp:63-70); setDr (:76-81) is read off w2n: dRdx = [[w10, w00], [-w00, w10]]
+__device__ inline void spa_set_transform(const double *pose, double *w)
+{
+    const double c = sdm_cos(pose[2]), s = sdm_sin(pose[2]);
+    w[0] = c; w[1] = s; w[3] = -s; w[4] = c;
+    // col(2) = -w2n * trans with col(2) zeroed first, trans = (x, y, 1): (w0*x + w1*y) + w2*t2
+    w[2] = -((w[0] * pose[0] + w[1] * pose[1]) + 0.0 * 1.0);
+    w[5] = -((w[3] * pose[0] + w[4] * pose[1]) + 0.0 * 1.0);
+}
+
+// Con2dP2::calcErr (spa2d.cpp:148-159): err, and the cost term err . (prec * err)
+__device__ inline double spa_calc_err(const double *w0, const double *p0, const double *p1, const double *mean,
+                                      const double *K, double *err)
+{
+    err[0] = ((w0[0] * p1[0] + w0[1] * p1[1]) + w0[2] * 1.0) - mean[0];
+    err[1] = ((w0[3] * p1[0] + w0[4] * p1[1]) + w0[5] * 1.0) - mean[1];
+    double aerr = (p1[2] - p0[2]) - mean[2];
+    if (aerr > SDM_PI) aerr -= 2.0 * SDM_PI;
+    if (aerr < -SDM_PI) aerr += 2.0 * SDM_PI;
+    err[2] = aerr;
+    double pe[3];
+    spa_mv3(K, err, pe);
+    return spa_dot3(err, pe);
+}
+
+// The fixed reduction shape (spa.h): the lanes' partial sums, then s[t] += s[t + 128], ..., s[0] += s[1].  Every
+// lane returns lane 0's sum, read from LDS.
+__device__ inline double spa_reduce(double v, double *red)
+{
+    const int t = threadIdx.x;
+    red[t] = v;
+    __syncthreads();
+    for (int o = SPA_THREADS / 2; o > 0; o >>= 1) {
+        if (t < o) red[t] = red[t] + red[t + o];
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+
+// calcCost (spa2d.cpp:173-201): the sum over constraints, in the reduction shape
+__device__ inline double spa_cost(int m, const int2 *nd, const double *mean, const double *prec, const double *w2n,
+                                  const double *poses, double *red)
+{
+    double acc = 0.0;
+    for (int ci = threadIdx.x; ci < m; ci += SPA_THREADS) {
+        const int2 e = nd[ci];
+        double err[3];
+        acc += spa_calc_err(w2n + 6 * e.x, poses + 3 * e.x, poses + 3 * e.y, mean + 3 * ci, prec + 9 * ci, err);
+    }
+    return spa_reduce(acc, red);
+}
+
+__global__ __launch_bounds__(SPA_THREADS) void spa_solve_kernel(SpaDev D, int g_first, spa_params P)
+{
+    __shared__ double red[SPA_THREADS];
+    __shared__ int bc[5];
+    const int t = threadIdx.x;
+    const int g = g_first + blockIdx.x;
+    const size_t N = (size_t)D.max_nodes, M = (size_t)D.max_cons;
+
+    if (t == 0) {
+        const SpaHdr h = D.hdr[g];
+        bc[0] = h.n_nodes;
+        bc[1] = h.n_cons;
+        bc[2] = h.n_pairs;
+        bc[3] = 0;
+        bc[4] = h.n_fixed == SPA_FIXED_FROM_PARAMS ? P.n_fixed : h.n_fixed;
+    }
+    __syncthreads();
+    const int n = bc[0], m = bc[1], npairs = bc[2], n_fixed = bc[4];
+    const int nF = n_fixed < n ? n_fixed : n;  // nodes [0, nF) are fixed
+    const int nfree = n - nF;
+
+    double *poses = D.poses + g * N * 3;
+    const int2 *con_nd = D.con_nd + g * M;
+    const double *con_mean = D.con_mean + g * M * 3;
+    const double *con_prec = D.con_prec + g * M * 9;
+    const int *inc_off = D.inc_off + g * (N + 1);
+    const int *inc = D.inc + g * 2 * M;
+    const int *nbr_off = D.nbr_off + g * (N + 1);
+    const int2 *nbr = D.nbr + g * 2 * M;
+    const int *pair_off = D.pair_off + g * (M + 1);
+    const int *pair_con = D.pair_con + g * M;
+    double *sc = D.scratch + g * spa_scratch_doubles(D.max_nodes, D.max_cons);
+    double *w2n = sc;            sc += N * 6;
+    double *diag = sc;           sc += N * 9;
+    double *jinv = sc;           sc += N * 9;
+    double *vB = sc;             sc += N * 3;
+    double *vx = sc;             sc += N * 3;
+    double *vr = sc;             sc += N * 3;
+    double *vd = sc;             sc += N * 3;
+    double *vq = sc;             sc += N * 3;
+    double *vs = sc;             sc += N * 3;
+    double *old = sc;            sc += N * 3;
+    double *cs = sc;             sc += M * SPA_CON_DOUBLES;
+    double *pblk = sc;
+
+    spa_stats st;
+    st.status = SPA_OK;
+    st.good_iter = st.lm_iters = st.rejected = st.cg_iters = st.converged = 0;
+    st.initial_cost = st.final_cost = 0.0;
+    st.lambda = P.lambda;
+
+    // "No fixed frames" (spa2d.cpp:435-439): nothing is touched
+    if (n_fixed <= 0) {
+        st.status = SPA_NO_FIXED;
+        if (t == 0) D.stats[g] = st;
+        return;
+    }
+    // a free node without a constraint (the dcnt count of setupSparseSys, spa2d.cpp:407-412): refused
+    {
+        int lone = 0;
+        for (int i = t; i < nfree; i += SPA_THREADS) {
+            const int k = nF + i;
+            if (inc_off[k + 1] == inc_off[k]) lone = 1;
+        }
+        if (lone) bc[3] = 1;
+        __syncthreads();
+        if (bc[3]) {
+            st.status = SPA_DISCONNECTED;
+            if (t == 0) D.stats[g] = st;
+            return;
+        }
+    }
+
+    // doSPA :440-449: every node's world-to-node transform
+    for (int k = t; k < n; k += SPA_THREADS) spa_set_transform(poses + 3 * k, w2n + 6 * k);
+    __syncthreads();
+
+    double lambda = P.lambda;  // :452-453
+    double laminc = 2.0;       // :455
+    const double lamdec = 0.5; // :456
+    const double sqMinDelta = 1e-8 * 1e-8;  // :458
+    double cost = spa_cost(m, con_nd, con_mean, con_prec, w2n, poses, red);  // :459
+    st.initial_cost = cost;
+    double residual = 0.0;  // jacobiBPCG::residual; read only when abstol, i.e. after this call has set it
+
+    int iter = 0;
+    for (; iter < P.niter; ++iter) {  // :466
+        st.lm_iters = iter + 1;
+        // ---- setupSparseSys (:328-413), per constraint: setJacobians (:86-142) and the products of :351-392
+        for (int ci = t; ci < m; ci += SPA_THREADS) {
+            const int2 e = con_nd[ci];
+            const int k0 = e.x, k1 = e.y;
+            const double *w = w2n + 6 * k0, *p0 = poses + 3 * k0, *p1 = poses + 3 * k1, *K = con_prec + 9 * ci;
+            double err[3];
+            spa_calc_err(w, p0, p1, con_mean + 3 * ci, K, err);  // con.err as the last calcCost left it
+            // pwt = (t1 - tr).head(2); dp = dRdx * pwt
+            const double pw0 = p1[0] - p0[0], pw1 = p1[1] - p0[1];
+            const double dp0 = w[3] * pw0 + w[0] * pw1;
+            const double dp1 = (-w[0]) * pw0 + w[3] * pw1;
+            const double J0[9] = {-w[0], -w[1], dp0, -w[3], -w[4], dp1, 0.0, 0.0, -1.0};
+            const double J1[9] = {w[0], w[1], 0.0, w[3], w[4], 0.0, 0.0, 0.0, 1.0};
+            double J0t[9], J1t[9], T[9], tp[9];
+            spa_tr33(J0, J0t);
+            spa_tr33(J1, J1t);
+            double *o = cs + (size_t)ci * SPA_CON_DOUBLES;
+            const bool f0 = k0 >= nF, f1 = k1 >= nF;
+            if (f0) {
+                spa_mul33(J0t, K, T);      // J0t * prec
+                spa_mul33(T, J0, o);       // ... * J0                         (:362)
+                spa_mv3(T, err, o + 27);   // J0t * prec * err                 (:389)
+            }
+            if (f1) {
+                spa_mul33(K, J1, tp);      // tp = prec * J1                   (:369)
+                spa_mul33(J1t, tp, o + 9); // J1t * tp                         (:370)
+                if (f0) {
+                    double m2[9];
+                    spa_mul33(J0t, tp, m2);  // J0t * tp                       (:374)
+                    if (k1 < k0) spa_tr33(m2, o + 18);  // block (i1, i0)      (:375-379)
+                    else
+                        for (int q = 0; q < 9; ++q) o[18 + q] = m2[q];  // block (i0, i1) (:382)
+                }
+                spa_mul33(J1t, K, T);
+                spa_mv3(T, err, o + 30);   // J1t * prec * err                 (:391)
+            }
+        }
+        __syncthreads();
+        // ---- per free node: addDiagBlock / B -= in constraint order (csparse.h:166-167, spa2d.cpp:389-391),
+        // incDiagBlocks (csparse.cpp:488-492), the Jacobi preconditioner and PCG's start (bpcg.h:278-287)
+        const double lam = 1.0 + lambda;  // :348
+        double acc = 0.0;
+        for (int i = t; i < nfree; i += SPA_THREADS) {
+            const int k = nF + i;
+            double A[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, b[3] = {0.0, 0.0, 0.0};
+            for (int j = inc_off[k]; j < inc_off[k + 1]; ++j) {
+                const int ci = inc[j] >> 1, end = inc[j] & 1;
+                const double *o = cs + (size_t)ci * SPA_CON_DOUBLES;
+                for (int q = 0; q < 9; ++q) A[q] += o[9 * end + q];
+                for (int q = 0; q < 3; ++q) b[q] -= o[27 + 3 * end + q];
+            }
+            A[0] *= lam; A[4] *= lam; A[8] *= lam;
+            double Ji[9], dd[3];
+            spa_inv33(A, Ji);
+            spa_mv3(Ji, b, dd);  // r = b; mD(J, r, d)
+            for (int q = 0; q < 9; ++q) {
+                diag[9 * k + q] = A[q];
+                jinv[9 * k + q] = Ji[q];
+            }
+            for (int q = 0; q < 3; ++q) {
+                vB[3 * k + q] = b[q];
+                vr[3 * k + q] = b[q];
+                vd[3 * k + q] = dd[q];
+                vx[3 * k + q] = 0.0;
+            }
+            acc += spa_dot3(b, dd);
+        }
+        // ---- per node pair with both ends free: addOffdiagBlock (csparse.cpp:472-485).  On a call's first
+        // iteration the pair's first constraint is inserted as it is; later the blocks are zeroed (:445-459) and
+        // every constraint is added, the first onto +0.0
+        for (int p = t; p < npairs; p += SPA_THREADS) {
+            const int j0 = pair_off[p], j1 = pair_off[p + 1];
+            const int2 e = con_nd[pair_con[j0]];
+            if ((e.x < e.y ? e.x : e.y) < nF) continue;
+            double Bk[9];
+            const double *o = cs + (size_t)pair_con[j0] * SPA_CON_DOUBLES + 18;
+            for (int q = 0; q < 9; ++q) Bk[q] = iter == 0 ? o[q] : 0.0 + o[q];
+            for (int j = j0 + 1; j < j1; ++j) {
+                o = cs + (size_t)pair_con[j] * SPA_CON_DOUBLES + 18;
+                for (int q = 0; q < 9; ++q) Bk[q] += o[q];
+            }
+            for (int q = 0; q < 9; ++q) pblk[9 * (size_t)p + q] = Bk[q];
+        }
+        // ---- doBPCG (csparse.cpp:737-749) -> doBPCG2 (bpcg.h:284-315); skipped when B has no rows (:485)
+        if (nfree > 0) {
+            double dn = spa_reduce(acc, red);  // r.dot(d); its barriers also publish d and the pair blocks
+            double d0 = P.init_tol * dn;
+            if (iter > 0) {  // abstol (csparse.cpp:743-744)
+                if (residual > d0) d0 = residual;
+            }
+            int i = 0;
+            for (; i < P.max_cg_iters; ++i) {
+                if (dn < d0) break;
+                // mMV2 (bpcg.h:142-161) as a gather: the diagonal block, then the neighbours in ascending index
+                acc = 0.0;
+                for (int f = t; f < nfree; f += SPA_THREADS) {
+                    const int k = nF + f;
+                    double q3[3], u[3];
+                    spa_mv3(diag + 9 * k, vd + 3 * k, q3);
+                    for (int j = nbr_off[k]; j < nbr_off[k + 1]; ++j) {
+                        const int2 nb = nbr[j];
+                        if (nb.x < nF) continue;
+                        if (nb.x < k) spa_mtv3(pblk + 9 * (size_t)nb.y, vd + 3 * nb.x, u);  // vout(ii) += M' vin(ri)
+                        else spa_mv3(pblk + 9 * (size_t)nb.y, vd + 3 * nb.x, u);            // vout(ri) += M vin(ii)
+                        for (int q = 0; q < 3; ++q) q3[q] += u[q];
+                    }
+                    for (int q = 0; q < 3; ++q) vq[3 * k + q] = q3[q];
+                    acc += spa_dot3(vd + 3 * k, q3);
+                }
+                const double a = dn / spa_reduce(acc, red);  // :300
+                acc = 0.0;
+                for (int f = t; f < nfree; f += SPA_THREADS) {
+                    const int k = nF + f;
+                    double r3[3], s3[3];
+                    for (int q = 0; q < 3; ++q) {
+                        vx[3 * k + q] = vx[3 * k + q] + a * vd[3 * k + q];  // x += a*d
+                        r3[q] = vr[3 * k + q] - a * vq[3 * k + q];          // r -= a*q
+                        vr[3 * k + q] = r3[q];
+                    }
+                    spa_mv3(jinv + 9 * k, r3, s3);  // mD(J, r, s)
+                    for (int q = 0; q < 3; ++q) vs[3 * k + q] = s3[q];
+                    acc += spa_dot3(r3, s3);
+                }
+                const double dold = dn;
+                dn = spa_reduce(acc, red);  // :306
+                const double ba = dn / dold;
+                for (int f = t; f < nfree; f += SPA_THREADS) {
+                    const int k = nF + f;
+                    for (int q = 0; q < 3; ++q) vd[3 * k + q] = vs[3 * k + q] + ba * vd[3 * k + q];  // d = s + ba*d
+                }
+                __syncthreads();
+            }
+            residual = dn / 2.0;  // :314
+            st.cg_iters += i;
+        } else {
+            __syncthreads();
+        }
+        // ---- B = x (csparse.cpp:747); sqDiff = BB.squaredNorm() (:523)
+        acc = 0.0;
+        for (int f = t; f < nfree; f += SPA_THREADS) {
+            const int k = nF + f;
+            acc += spa_dot3(vx + 3 * k, vx + 3 * k);
+        }
+        const double sqDiff = spa_reduce(acc, red);
+        if (sqDiff < sqMinDelta) {  // :524-529
+            st.converged = 1;
+            break;
+        }
+        // ---- update the frames (:532-546)
+        for (int f = t; f < nfree; f += SPA_THREADS) {
+            const int k = nF + f;
+            double *p = poses + 3 * k;
+            for (int q = 0; q < 3; ++q) old[3 * k + q] = p[q];
+            p[0] += vx[3 * k];
+            p[1] += vx[3 * k + 1];
+            double a = p[2] + vx[3 * k + 2];
+            if (a > SDM_PI) a -= 2.0 * SDM_PI;  // normArot (spa2d.h:106-110)
+            if (a < -SDM_PI) a += 2.0 * SDM_PI;
+            p[2] = a;
+            spa_set_transform(p, w2n + 6 * k);
+        }
+        __syncthreads();
+        const double newcost = spa_cost(m, con_nd, con_mean, con_prec, w2n, poses, red);  // :549
+        if (newcost < cost) {  // :555-561
+            cost = newcost;
+            lambda *= lamdec;
+            st.good_iter++;
+        } else {  // :562-582
+            lambda *= laminc;
+            laminc *= 2.0;
+            for (int f = t; f < nfree; f += SPA_THREADS) {
+                const int k = nF + f;
+                double *p = poses + 3 * k;
+                for (int q = 0; q < 3; ++q) p[q] = old[3 * k + q];
+                spa_set_transform(p, w2n + 6 * k);
+            }
+            __syncthreads();
+            cost = spa_cost(m, con_nd, con_mean, con_prec, w2n, poses, red);
+            st.rejected++;
+        }
+    }
+    st.final_cost = cost;
+    st.lambda = lambda;
+    if (t == 0) D.stats[g] = st;
+}
+
+}  // namespace s2d

@@ -1,0 +1,30 @@
+"""Write tests/golden/spa_cases.npz: the inputs of the named pose graphs (spa2d_ref.golden_cases) and what the CPU
+restatement (tests/ref/spa2d_ref.c) gives for them -- final poses and the stats.  tests/test_spa_cpu.py replays the
+restatement against the file, so a silent change of the restatement shows up; tests/test_spa_gpu.py runs the same
+cases on the device.  Numeric arrays only.
+
+    python tests/ref/make_spa_golden.py [output.npz]
+"""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import spa2d_ref as R  # noqa: E402
+
+
+def main(path: str) -> None:
+    cases = {}
+    for name, c in R.golden_cases().items():
+        po, st = R.compute_case(c)
+        cases[name] = (c, po, st)
+        print(f"{name:10s} nodes {len(c['poses']):4d} cons {len(c['ends']):4d}  lm {st['lm_iters']:3d} good "
+              f"{st['good_iter']:3d} rejected {st['rejected']:2d} cg {st['cg_iters']:4d} converged {st['converged']} "
+              f"cost {st['initial_cost']:.6g} -> {st['final_cost']:.6g}")
+    np.savez_compressed(path, **R.pack_golden(cases))
+    print(path, os.path.getsize(path), "bytes")
+
+
+if __name__ == "__main__":
+    main(sys.argv[1] if len(sys.argv) > 1 else R.GOLDEN)
