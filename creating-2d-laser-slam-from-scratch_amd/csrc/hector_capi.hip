@@ -41,7 +41,6 @@ int fail(int code, const char *what, hipError_t e = hipSuccess)
     } while (0)
 
 constexpr int NKERN = 3;
-constexpr int MAX_PARTS = 4;
 
 struct EventPair {
     hipEvent_t a, b;
@@ -50,6 +49,7 @@ struct EventPair {
 }  // namespace
 
 struct hs_ctx {
+    HsOptions opt;  // the environment's knobs as read at hs_create (hector_internal.h; table: DESIGN.md section 5)
     int B = 0, levels = 0, max_points = 0, sx = 0, sy = 0;
     float res = 0, start_x = 0, start_y = 0;
     FleetGeom geom{};
@@ -79,18 +79,8 @@ struct hs_ctx {
     WorkQueue *d_wq = nullptr;  // one queue per part
     unsigned seg_cap = 0, item_cap = 0;  // per part
     int tile_grid = 0;
-    // batch split into parts on separate HIP streams so one part's tile kernel overlaps another
-    // part's match / bin kernels (they are latency-bound at low occupancy)
-    int nparts = 1;
-    // queue slots (work queue, segment / item / whole ranges) = parts that can be in flight: nparts, and at
-    // least 2 when the pipelined run (SLAM2D_PIPELINE=1) drives the two fleet halves as parts 0 and 1
-    int nq = 1;
-    int update_single = 1;  // hs_update_kernel (per stream-level, default) or bin + tile kernels
-    // the single-kernel update: the round-3 hs_update_kernel (per-tile clipping; default) or
-    // hs_update_ring_kernel (ring-ordered tiles, ray cursors; SLAM2D_UPD_KERNEL=ring, scans of <= 1280 points)
-    bool upd_ring = false;
     int ncu = 256;
-    bool upd_parts_fixed = false;  // SLAM2D_UPD_PARTS given: no batch-size adaptive split
+    bool big = false;  // a level of 2^30 words or more (init_geometry; hs_match_kernel BIG)
     // per part (a batch split over part streams): two alternating lists of updating streams
     // (hector_internal.h UpdList): the match kernel appends to one, the update kernel reads it and
     // clears the other for the next step
@@ -98,16 +88,9 @@ struct hs_ctx {
     int wl_parity[MAX_PARTS] = {};
     hipStream_t pstream[MAX_PARTS] = {};
     hipEvent_t ev_start = nullptr, ev_done[MAX_PARTS] = {};
-    // hs_run_ranges_device pipeline (SLAM2D_PIPELINE=1): update of one half of the fleet beside the other
-    // half's match.  Measured slower at the north-star size (0.97 M vs 1.04 M scans/s: the update
-    // kernel already fills the CUs, and a concurrent match slows it more than it hides), so off by default.
-    bool pipeline = false;
-    // ordinal sweep (hector_internal.h ORD_OFF): steps since the last one, and the interval (SLAM2D_ORD_SWEEP, tests)
-    int ord_steps = 0;
-    int ord_interval = ORD_SWEEP_MAX;
-    bool fuse_ingest = true;  // range arrays: ingest inside the match kernel (SLAM2D_FUSE_INGEST=0: own kernel)
+    int ord_steps = 0;  // ordinal sweep (hector_internal.h ORD_OFF): steps since the last one
     // Hessian summation order of hs_match_kernel: 0 = the reference's sequential point order (default),
-    // 256 = the 256-thread tree (hs_set_reduction_order / SLAM2D_MATCH_ORDER=tree)
+    // 256 = the 256-thread tree (hs_set_reduction_order; opt.reduce_order at hs_create)
     int reduce_order = 0;
     hipEvent_t ev_upd[MAX_PARTS] = {};
     // the last device work of the context (every *_device call waits for it on its own stream, so the
@@ -129,7 +112,6 @@ struct hs_ctx {
     float *d_ranges1 = nullptr;
     // clock probe buffer (hs_set_clock_probe): 8 counters, see FleetGeom::clk
     unsigned long long *d_clk = nullptr;
-    size_t stream_pad_words = 0;  // see init_geometry
 };
 
 namespace {
@@ -170,6 +152,7 @@ void init_geometry(hs_ctx *c)
         L.tiles_y = (ry + TILE_H - 1) / TILE_H;
         L.word_offset = off;
         off += (size_t)L.tiles_x * L.tiles_y * TILE_BLOCK_WORDS;
+        c->big = c->big || (unsigned long long)L.tiles_x * L.tiles_y * TILE_BLOCK_WORDS >= (1ull << 30);
         rx /= 2;
         ry /= 2;
         res *= 2.0f;
@@ -177,7 +160,7 @@ void init_geometry(hs_ctx *c)
     // per-stream pad (SLAM2D_STREAM_PAD bytes, a multiple of 256): a stream's levels add up to a multiple of
     // 2 MB, so without it the same tile of every stream sits at the same offset modulo every power-of-two
     // interleave period of the memory system
-    g.stream_words = off + c->stream_pad_words;
+    g.stream_words = off + c->opt.stream_pad_words;
     g.cells_words = off;
 }
 
@@ -260,152 +243,64 @@ void end_timed(hs_ctx *c, hipStream_t s)
     hipEventRecord(c->ev_used.back().b, s);
 }
 
-// hs_update_kernel instance: rays in registers for scans of at most UPD_RREG * 256 points (no LDS ray
-// array), else in LDS; SLAM2D_UPD_RAYS_LDS=1 forces the LDS instance (A/B)
-bool upd_rays_in_regs(const hs_ctx *c)
-{
-    static const bool force_lds = getenv("SLAM2D_UPD_RAYS_LDS") && atoi(getenv("SLAM2D_UPD_RAYS_LDS")) != 0;
-    return !force_lds && c->max_points <= UPD_RREG * UPD_THREADS;
-}
+HsShape shape(const hs_ctx *c) { return HsShape{c->B, c->levels, c->max_points, c->sx, c->sy, c->ncu, c->big, c->ingest.n}; }
 
-size_t upd_shmem_bytes(const hs_ctx *c)
-{
-    const size_t rays = upd_rays_in_regs(c) ? 0 : (size_t)((c->max_points + 3) & ~3);
-    return sizeof(unsigned) * ((size_t)UPD_FIXED_WORDS + rays + UPD_GROUP_WORDS * (size_t)fan_groups(c->max_points));
-}
-
-// hs_update_kernel's packed raster walk keeps the Bresenham error f < da in 14 bits (V = f << 18 | LDS
-// address): rays of at most 16384 cells, i.e. level-0 maps of at most 16385 cells per side.  Larger maps
-// take the binned kernels (their walk keeps the error in its own register), as do scans whose rays would
-// not fit the kernel's LDS (the binned kernels' LDS use is independent of the scan size).
-bool upd_single_ok(const hs_ctx *c)
-{
-    return c->update_single && upd_shmem_bytes(c) <= 65536 && c->sx <= 16385 && c->sy <= 16385;
-}
-
-size_t ring_shmem_bytes(const hs_ctx *c) { return sizeof(unsigned) * (size_t)ring_shmem_words(c->max_points); }
-
-// hs_update_ring_kernel: rays in registers (<= RING_GROUPS * 256 points), da / db in 14 bits (<= 16384
-// cells per side)
-bool upd_ring_ok(const hs_ctx *c)
-{
-    return c->upd_ring && c->max_points <= 5 * 256 && c->sx <= 16384 && c->sy <= 16384;
-}
-
-// (defined after launch_part, so that the library keeps its kernels in the order match, then update)
-int launch_update(hs_ctx *c, const FleetGeom &geom, int blocks, const float2 *xy, int xy_stride, int begin, int count,
-                  const UpdList *wl_cur, UpdList *wl_next, hipStream_t s);
-
+// One part of a step: plan (hector_internal.h plan_step), the match instance, the update.
 int launch_part(hs_ctx *c, int part, int begin, int count, const float2 *xy, int xy_stride, const int *n,
                 const float2 *origo, const float *hints, int mode, float *out_pose, float *out_cov, hipStream_t s,
                 hipEvent_t wait_before_update = nullptr, const MatchIngest *mi = nullptr)
 {
-    if (part < 0 || part >= c->nq) return fail(HS_EINVAL, "internal: part without a queue slot");
+    if (part < 0 || part >= c->opt.nq) return fail(HS_EINVAL, "internal: part without a queue slot");
+    const StepPlan plan = plan_step(c->opt, shape(c), c->reduce_order, count, mode);
     WorkQueue *wq = c->d_wq + part;
-    uint4 *segs = c->d_segs + (size_t)part * c->seg_cap;
-    WorkItem *items = c->d_items + (size_t)part * c->item_cap;
-    WorkItem *wholes = c->d_wholes + (size_t)part * c->B * c->levels;
     // the single-kernel update consumes the match kernel's list of updating streams (wl[part][parity]: one
     // pair of lists per part)
-    const bool single = upd_single_ok(c);
-    const bool use_list = single && !c->upd_parts_fixed && mode != MODE_MATCH_ONLY;
-    UpdList *wl_cur = use_list ? c->wl[part][c->wl_parity[part]] : nullptr;
+    UpdList *wl_cur = plan.use_list ? c->wl[part][c->wl_parity[part]] : nullptr;
     begin_timed(c, 0, s);
-    // the register-only instance when no scan of the context can exceed the kernel's register slots
     const MatchIngest mik = mi ? *mi : MatchIngest{};
 #define S2D_MATCH_LAUNCH(SEQ, REGS, BIG)                                                                                 \
     hipLaunchKernelGGL((hs_match_kernel<SEQ, REGS, BIG>), dim3(count), dim3(MATCH_THREADS), 0, s, c->geom, c->d_cells,    \
                        c->d_state, xy, xy_stride, n, origo, hints, begin, mode, out_pose, out_cov, c->plog, wq, wl_cur,   \
                        c->ingest, mik, c->d_ixy, c->max_points)
-    // a level of 2^30 words or more: the gathers' 32-bit byte offsets would overflow (hs_match_kernel BIG)
-    bool big = false;
-    for (int l = 0; l < c->levels; ++l)
-        big = big || (unsigned long long)c->geom.lv[l].tiles_x * c->geom.lv[l].tiles_y * TILE_BLOCK_WORDS >= (1ull << 30);
-    if (c->reduce_order == 0) {
-        const bool regs = c->max_points <= CW_MAXN;
-        if (big) {
-            if (regs) S2D_MATCH_LAUNCH(true, true, true);
-            else S2D_MATCH_LAUNCH(true, false, true);
-        } else {
-            if (regs) S2D_MATCH_LAUNCH(true, true, false);
-            else S2D_MATCH_LAUNCH(true, false, false);
-        }
-    } else {
-        if (c->max_points <= MATCH_THREADS * MATCH_REG_PTS) S2D_MATCH_LAUNCH(false, true, false);
-        else S2D_MATCH_LAUNCH(false, false, false);
-    }
+    if (plan.big && plan.regs) S2D_MATCH_LAUNCH(true, true, true);  // (BIG is a reference-order instance)
+    else if (plan.big) S2D_MATCH_LAUNCH(true, false, true);
+    else if (plan.seq && plan.regs) S2D_MATCH_LAUNCH(true, true, false);
+    else if (plan.seq) S2D_MATCH_LAUNCH(true, false, false);
+    else if (plan.regs) S2D_MATCH_LAUNCH(false, true, false);
+    else S2D_MATCH_LAUNCH(false, false, false);
 #undef S2D_MATCH_LAUNCH
     end_timed(c, s);
     HCHK(hipGetLastError());
     if (mode == MODE_MATCH_ONLY) return HS_OK;
     if (wait_before_update) HCHK(hipStreamWaitEvent(s, wait_before_update, 0));
-    // hs_update_kernel keeps the scan's rays in LDS: beyond 64 KB of dynamic LDS (max_points > ~13k)
-    // the binned kernels, whose LDS use is independent of the scan size, take over
-    if (single && use_list) {
-        // grid for the largest split over U = 1 .. count updating streams; surplus workgroups exit
-        int blocks = 0;
-        for (int U = 1; U <= count; ++U) {
-            int pl[MAX_LEVELS], b = 0;
-            upd_split(U, c->ncu, c->levels, pl, c->geom.upd_minp);
-            for (int l = 0; l < c->levels; ++l) b += pl[l] * U;
-            blocks = b > blocks ? b : blocks;
-        }
-        UpdList *wl_next = c->wl[part][c->wl_parity[part] ^ 1];
-        c->wl_parity[part] ^= 1;
-        return launch_update(c, c->geom, blocks, xy, xy_stride, begin, count, wl_cur, wl_next, s);
+    // wl_next: the list the update clears for the next step's match (null lists: every stream of the batch, split
+    // by geom.upd_parts)
+    UpdList *wl_next = nullptr;
+    if (plan.use_list) wl_next = c->wl[part][c->wl_parity[part] ^= 1];
+#define S2D_UPDATE_LAUNCH(KERNEL, THREADS)                                                                               \
+    hipLaunchKernelGGL(KERNEL, dim3(plan.blocks), dim3(THREADS), plan.shmem, s, c->geom, c->d_cells, c->d_state, xy,      \
+                       xy_stride, c->d_ixy, c->max_points, begin, count, c->max_points, wl_cur, wl_next, c->ncu)
+    begin_timed(c, plan.upd == UPD_BINNED ? 1 : 2, s);
+    switch (plan.upd) {
+    case UPD_BINNED: {
+        uint4 *segs = c->d_segs + (size_t)part * c->seg_cap;
+        WorkItem *items = c->d_items + (size_t)part * c->item_cap;
+        WorkItem *wholes = c->d_wholes + (size_t)part * c->B * c->levels;
+        hipLaunchKernelGGL(hs_bin_kernel, dim3(count), dim3(BIN_THREADS), 0, s, c->geom, c->d_state, xy, xy_stride,
+                           c->d_ixy, c->max_points, begin, c->max_points, c->d_rays, segs, items, wholes, wq, c->seg_cap,
+                           c->item_cap);
+        end_timed(c, s);
+        HCHK(hipGetLastError());
+        begin_timed(c, 2, s);
+        hipLaunchKernelGGL(hs_tile_kernel, dim3(c->tile_grid), dim3(TILE_THREADS), 0, s, c->geom, c->d_cells, c->d_state,
+                           c->d_rays, segs, items, wholes, wq, c->max_points);
+        break;
     }
-    if (single) {
-        FleetGeom gg = c->geom;
-        if (!c->upd_parts_fixed) {
-            // small batches: split each level's tiles over several workgroups so that the grid fills the
-            // CUs (one level-0 workgroup of a 2048^2 scan takes ~0.4 ms alone; a part costs one ray setup)
-            // measured (2048^2 x 3, same box): B = 16: 2 per CU best; B = 64 .. 512: 4 per CU (+8 .. +33 %);
-            // B >= 1024: level 0 in 2 parts (neutral to +1.5 %)
-            const int target = count <= 32 ? 2 : 4;
-            int p0 = (target * c->ncu + count - 1) / count;
-            if (p0 < 2) p0 = 2;
-            if (c->levels == 1 && p0 < 8) p0 = 8;  // as upd_split: a single level fills the grid's tail alone
-            for (int l = 0; l < c->levels; ++l) {
-                const int v = p0 >> l;
-                gg.upd_parts[l] = v < 1 ? 1 : (v > 64 ? 64 : v);
-            }
-        }
-        int blocks = 0;
-        for (int l = 0; l < c->levels; ++l) blocks += gg.upd_parts[l] * count;
-        return launch_update(c, gg, blocks, xy, xy_stride, begin, count, nullptr, nullptr, s);
+    case UPD_RING: S2D_UPDATE_LAUNCH(hs_update_ring_kernel, RTHREADS); break;
+    case UPD_CLIP_REGS: S2D_UPDATE_LAUNCH((hs_update_kernel<UPD_RREG>), UPD_THREADS); break;
+    case UPD_CLIP_LDS: S2D_UPDATE_LAUNCH((hs_update_kernel<0>), UPD_THREADS); break;
     }
-    begin_timed(c, 1, s);
-    hipLaunchKernelGGL(hs_bin_kernel, dim3(count), dim3(BIN_THREADS), 0, s, c->geom, c->d_state, xy, xy_stride, c->d_ixy,
-                       c->max_points, begin, c->max_points, c->d_rays, segs, items, wholes, wq, c->seg_cap, c->item_cap);
-    end_timed(c, s);
-    HCHK(hipGetLastError());
-    begin_timed(c, 2, s);
-    hipLaunchKernelGGL(hs_tile_kernel, dim3(c->tile_grid), dim3(TILE_THREADS), 0, s, c->geom, c->d_cells, c->d_state,
-                       c->d_rays, segs, items, wholes, wq, c->max_points);
-    end_timed(c, s);
-    HCHK(hipGetLastError());
-    return HS_OK;
-}
-
-// The single-kernel grid update of one launch_part: the ring kernel, or hs_update_kernel with the rays in
-// registers or in LDS.  wl_cur / wl_next: the match kernel's lists of updating streams (null: every stream of
-// the batch, split by geom.upd_parts).
-int launch_update(hs_ctx *c, const FleetGeom &geom, int blocks, const float2 *xy, int xy_stride, int begin, int count,
-                  const UpdList *wl_cur, UpdList *wl_next, hipStream_t s)
-{
-    begin_timed(c, 2, s);
-    if (upd_ring_ok(c))
-        hipLaunchKernelGGL(hs_update_ring_kernel, dim3(blocks), dim3(RTHREADS), ring_shmem_bytes(c), s, geom, c->d_cells,
-                           c->d_state, xy, xy_stride, c->d_ixy, c->max_points, begin, count, c->max_points, wl_cur,
-                           wl_next, c->ncu);
-    else if (upd_rays_in_regs(c))
-        hipLaunchKernelGGL((hs_update_kernel<UPD_RREG>), dim3(blocks), dim3(UPD_THREADS), upd_shmem_bytes(c), s, geom,
-                           c->d_cells, c->d_state, xy, xy_stride, c->d_ixy, c->max_points, begin, count, c->max_points,
-                           wl_cur, wl_next, c->ncu);
-    else
-        hipLaunchKernelGGL((hs_update_kernel<0>), dim3(blocks), dim3(UPD_THREADS), upd_shmem_bytes(c), s, geom,
-                           c->d_cells, c->d_state, xy, xy_stride, c->d_ixy, c->max_points, begin, count, c->max_points,
-                           wl_cur, wl_next, c->ncu);
+#undef S2D_UPDATE_LAUNCH
     end_timed(c, s);
     HCHK(hipGetLastError());
     return HS_OK;
@@ -416,7 +311,7 @@ int launch_update(hs_ctx *c, const FleetGeom &geom, int blocks, const float2 *xy
 // 2 (k - E) + 2 stays below 2^16).  On stream s, after the previous steps and before this one.
 int ord_sweep_if_due(hs_ctx *c, hipStream_t s)
 {
-    if (c->ord_steps < c->ord_interval) {
+    if (c->ord_steps < c->opt.ord_interval) {
         ++c->ord_steps;
         return HS_OK;
     }
@@ -436,7 +331,7 @@ int launch_step(hs_ctx *c, int begin, int count, const float2 *xy, int xy_stride
 {
     if (count <= 0) return HS_OK;
     if (mode != MODE_MATCH_ONLY && ord_sweep_if_due(c, s) != HS_OK) return HS_EHIP;
-    const int parts = (mode == MODE_PROCESS && count >= 64 * c->nparts) ? c->nparts : 1;
+    const int parts = (mode == MODE_PROCESS && count >= 64 * c->opt.nparts) ? c->opt.nparts : 1;
     if (parts == 1)
         return launch_part(c, 0, begin, count, xy, xy_stride, n, origo, hints, mode, out_pose, out_cov, s, nullptr, mi);
     HCHK(hipEventRecord(c->ev_start, s));
@@ -465,12 +360,6 @@ int launch_step(hs_ctx *c, int begin, int count, const float2 *xy, int xy_stride
     return HS_OK;
 }
 
-// The pipelined run (hs_run_ranges_device) needs the list-driven single update kernel on every part.
-bool pipeline_ok(const hs_ctx *c)
-{
-    return c->pipeline && c->nq >= 2 && upd_single_ok(c) && !c->upd_parts_fixed && c->B >= 2;
-}
-
 int check_stream(hs_ctx *c, int stream) { return (c && stream >= 0 && stream < c->B) ? HS_OK : HS_EINVAL; }
 
 // *_device calls may name any HIP stream: order each call after the context's previous device work
@@ -496,12 +385,12 @@ int launch_ingest(hs_ctx *c, int count, const float *d_ranges, int range_stride,
 }
 
 // ingest + step on range arrays: the ingest runs inside the match kernel (one launch less) when the
-// scan fits the match kernel's registers (<= 1280 beams) unless SLAM2D_FUSE_INGEST=0; else its own kernel.
+// scan fits the match kernel's registers (plan_fused_ingest); else its own kernel.
 int launch_ranges_step(hs_ctx *c, int begin, int count, const float *d_ranges, int range_stride, float2 *xy,
                        int xy_stride, int *d_n, float2 *d_origo, const float *hints, float *out_pose, float *out_cov,
                        hipStream_t s)
 {
-    if (c->fuse_ingest && c->ingest.n <= MATCH_THREADS * MATCH_REG_PTS) {
+    if (plan_fused_ingest(c->opt, shape(c))) {
         const MatchIngest mi{d_ranges, range_stride, c->d_cs, xy, d_n, d_origo};
         return launch_step(c, begin, count, xy, xy_stride, d_n, d_origo, hints, MODE_PROCESS, out_pose, out_cov, s, &mi);
     }
@@ -545,16 +434,12 @@ int hs_create(hs_ctx **out, int num_streams, float map_resolution, int map_size_
         return fail(HS_EINVAL, "map too small for the requested number of levels");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HS_ENODEV, "no HIP device");
-    size_t pad_words = 0;
-    if (const char *sp = getenv("SLAM2D_STREAM_PAD")) {
-        // bytes between streams' pyramids: a non-negative multiple of 256 (whole 64-word granules)
-        char *end = nullptr;
-        const long long v = strtoll(sp, &end, 10);
-        if (end == sp || *end != '\0' || v < 0 || v % 256 != 0 || v > (1ll << 30))
-            return fail(HS_EINVAL, "SLAM2D_STREAM_PAD must be a non-negative multiple of 256 bytes (<= 1 GiB)");
-        pad_words = (size_t)(v / 256) * 64;
-    }
+    HsOptions opt;
+    const char *refused = parse_options(opt, [](const char *knob) -> const char * { return getenv(knob); });
+    if (refused) return fail(HS_EINVAL, refused);
     hs_ctx *c = new hs_ctx();
+    c->opt = opt;
+    c->reduce_order = opt.reduce_order;
     c->B = num_streams;
     c->levels = levels;
     c->max_points = max_points;
@@ -563,7 +448,6 @@ int hs_create(hs_ctx **out, int num_streams, float map_resolution, int map_size_
     c->res = map_resolution;
     c->start_x = map_start_x;
     c->start_y = map_start_y;
-    c->stream_pad_words = pad_words;
     init_geometry(c);
     c->geom.lf = prob_to_logodds(0.4f);  // GridMapLogOddsFunctions ctor (GridMapLogOdds.h:98-102)
     c->geom.lo = prob_to_logodds(0.6f);
@@ -606,63 +490,13 @@ int hs_create(hs_ctx **out, int num_streams, float map_resolution, int map_size_
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hs_tile_kernel, TILE_THREADS, 0) != hipSuccess ||
             per_cu < 1)
             per_cu = 4;
-        const char *tg = getenv("SLAM2D_TILE_WG_PER_CU");
-        c->tile_grid = ncu * (tg ? atoi(tg) : per_cu);
-        const char *pp = getenv("SLAM2D_PIPELINE");
-        c->pipeline = pp && atoi(pp) != 0;
-        const char *mo = getenv("SLAM2D_MATCH_ORDER");
-        c->reduce_order = (mo && strcmp(mo, "tree") == 0) ? MATCH_THREADS : 0;
-        const char *fi = getenv("SLAM2D_FUSE_INGEST");
-        c->fuse_ingest = !(fi && atoi(fi) == 0);
-        // steps between ordinal sweeps (tests set a few to exercise the sweep; at most ORD_SWEEP_MAX).  0: never
-        // (TEST ONLY: stands for a caller that replays graph captures of *_device calls without hs_flush_ordinals,
-        // to exercise the device's ordinal-overflow flag)
-        if (const char *os = getenv("SLAM2D_ORD_SWEEP")) {
-            const int v = atoi(os);
-            c->ord_interval = v == 0 ? INT_MAX : (v < 1 ? 1 : (v > ORD_SWEEP_MAX ? ORD_SWEEP_MAX : v));
-        }
-        const char *np = getenv("SLAM2D_PARTS");
-        c->nparts = np ? atoi(np) : 1;
-        const char *um = getenv("SLAM2D_UPDATE");
-        c->update_single = (um && strcmp(um, "binned") == 0) ? 0 : 1;  // measured: single 1.06 ms vs binned 1.30 ms
-        // measured (round 4, profiles/r04/ab_r04c.md): ring 1.084 ms vs clip 0.924 ms per 2048-stream launch --
-        // the ring kernel's cursors save little VALU and its tile enumeration costs SALU; opt-in only
-        const char *uk = getenv("SLAM2D_UPD_KERNEL");
-        c->upd_ring = uk && strcmp(uk, "ring") == 0;
-        // workgroups per (stream, level) of hs_update_kernel: adaptive (launch_part: 1 at >= 512 streams,
-        // where splitting measured neutral to slower), or fixed by SLAM2D_UPD_PARTS="p0,p1,..." 
-        for (int l = 0; l < MAX_LEVELS; ++l) c->geom.upd_parts[l] = 1;
+        c->tile_grid = ncu * (opt.tile_wg_set ? opt.tile_wg_per_cu : per_cu);
         c->ncu = ncu;
-        if (const char *up = getenv("SLAM2D_UPD_PARTS")) {
-            c->upd_parts_fixed = true;
-            int l = 0;
-            for (const char *q = up; *q && l < MAX_LEVELS; ++l) {
-                const int v = atoi(q);
-                c->geom.upd_parts[l] = v < 1 ? 1 : (v > 64 ? 64 : v);
-                while (*q && *q != ',') ++q;
-                if (*q == ',') ++q;
-            }
-            for (; l < MAX_LEVELS; ++l) c->geom.upd_parts[l] = c->geom.upd_parts[l - 1];
-        }
-        // list-driven split: minimum workgroups per level, SLAM2D_UPD_SPLIT="m0,m1,..." (default: upd_split's)
-        for (int l = 0; l < MAX_LEVELS; ++l) c->geom.upd_minp[l] = 0;
-        if (const char *us = getenv("SLAM2D_UPD_SPLIT")) {
-            int l = 0;
-            for (const char *q = us; *q && l < MAX_LEVELS; ++l) {
-                const int v = atoi(q);
-                c->geom.upd_minp[l] = v < 0 ? 0 : (v > 64 ? 64 : v);
-                while (*q && *q != ',') ++q;
-                if (*q == ',') ++q;
-            }
-        }
-        if (c->nparts < 1) c->nparts = 1;
-        if (c->nparts > MAX_PARTS) c->nparts = MAX_PARTS;
-        c->nq = (c->pipeline && c->nparts < 2) ? 2 : c->nparts;
-        // per-part capacities (test hooks SLAM2D_SEG_CAP / SLAM2D_ITEM_CAP set them directly)
-        if (const char *e2 = getenv("SLAM2D_SEG_CAP")) c->seg_cap = (unsigned)atoll(e2);
-        else c->seg_cap = (unsigned)((size_t)c->seg_cap / c->nq + (1u << 16));
-        if (const char *e2 = getenv("SLAM2D_ITEM_CAP")) c->item_cap = (unsigned)atoll(e2);
-        else c->item_cap = (unsigned)((size_t)c->item_cap / c->nq + (1u << 10));
+        memcpy(c->geom.upd_parts, opt.upd_parts, sizeof(opt.upd_parts));
+        memcpy(c->geom.upd_minp, opt.upd_minp, sizeof(opt.upd_minp));
+        // per-part capacities
+        c->seg_cap = opt.seg_cap_set ? opt.seg_cap : (unsigned)((size_t)c->seg_cap / opt.nq + (1u << 16));
+        c->item_cap = opt.item_cap_set ? opt.item_cap : (unsigned)((size_t)c->item_cap / opt.nq + (1u << 10));
         for (int p = 0; p < MAX_PARTS; ++p) {
             if ((e = hipStreamCreateWithFlags(&c->pstream[p], hipStreamDefault)) != hipSuccess ||
                 (e = hipEventCreateWithFlags(&c->ev_done[p], hipEventDisableTiming)) != hipSuccess ||
@@ -678,10 +512,10 @@ int hs_create(hs_ctx **out, int num_streams, float map_resolution, int map_size_
         }
     }
     if ((e = hipMalloc(&c->d_rays, sizeof(unsigned) * (size_t)num_streams * levels * max_points)) != hipSuccess ||
-        (e = hipMalloc(&c->d_segs, sizeof(uint4) * (size_t)c->seg_cap * c->nq)) != hipSuccess ||
-        (e = hipMalloc(&c->d_items, sizeof(WorkItem) * (size_t)c->item_cap * c->nq)) != hipSuccess ||
-        (e = hipMalloc(&c->d_wholes, sizeof(WorkItem) * (size_t)num_streams * levels * c->nq)) != hipSuccess ||
-        (e = hipMalloc(&c->d_wq, sizeof(WorkQueue) * c->nq)) != hipSuccess) {
+        (e = hipMalloc(&c->d_segs, sizeof(uint4) * (size_t)c->seg_cap * c->opt.nq)) != hipSuccess ||
+        (e = hipMalloc(&c->d_items, sizeof(WorkItem) * (size_t)c->item_cap * c->opt.nq)) != hipSuccess ||
+        (e = hipMalloc(&c->d_wholes, sizeof(WorkItem) * (size_t)num_streams * levels * c->opt.nq)) != hipSuccess ||
+        (e = hipMalloc(&c->d_wq, sizeof(WorkQueue) * c->opt.nq)) != hipSuccess) {
         hs_destroy(c);
         return fail(HS_ENOMEM, "hipMalloc", e);
     }
@@ -696,7 +530,7 @@ int hs_create(hs_ctx **out, int num_streams, float map_resolution, int map_size_
         memset(&q, 0, sizeof(q));
         q.item_cap = c->item_cap;
         q.seg_cap = c->seg_cap;
-        for (int p = 0; p < c->nq; ++p) {
+        for (int p = 0; p < c->opt.nq; ++p) {
             if ((e = hipMemcpy(c->d_wq + p, &q, sizeof(q), hipMemcpyHostToDevice)) != hipSuccess) {
                 hs_destroy(c);
                 return fail(HS_EHIP, "hipMemcpy(work queue)", e);
@@ -995,7 +829,7 @@ int hs_run_ranges_device(hs_ctx *c, int steps, const float *d_ranges, int range_
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
     int rc = dev_enter(c, s);
     if (rc != HS_OK) return rc;
-    if (!pipeline_ok(c)) {  // default: the steps in order on s
+    if (!plan_pipeline(c->opt, shape(c))) {  // default: the steps in order on s
         for (int k = 0; k < steps && rc == HS_OK; ++k)
             rc = launch_ranges_step(c, 0, c->B, d_ranges + (size_t)k * step_stride, range_stride, c->d_ixy, c->max_points,
                                     c->d_in, c->d_iorigo, nullptr, nullptr, nullptr, s);
@@ -1011,7 +845,7 @@ int hs_run_ranges_device(hs_ctx *c, int steps, const float *d_ranges, int range_
     for (int h = 0; h < 2; ++h) HCHK(hipStreamWaitEvent(c->pstream[h], c->ev_start, 0));
     for (int k = 0; k < steps && rc == HS_OK; ++k) {
         const float *rk = d_ranges + (size_t)k * step_stride;
-        if (c->ord_steps + 1 > c->ord_interval) {
+        if (c->ord_steps + 1 > c->opt.ord_interval) {
             // an ordinal sweep is due: after both halves' previous updates, before either half's next step
             for (int h = 0; h < 2; ++h) {
                 HCHK(hipEventRecord(c->ev_done[h], c->pstream[h]));
@@ -1207,10 +1041,10 @@ int hs_get_queue_stats(hs_ctx *c, int64_t out[8], int reset_stamps)
     WorkQueue q[MAX_PARTS];
     unsigned long long st[8];
     HCHK(hipDeviceSynchronize());
-    HCHK(hipMemcpy(q, c->d_wq, sizeof(WorkQueue) * c->nq, hipMemcpyDeviceToHost));
+    HCHK(hipMemcpy(q, c->d_wq, sizeof(WorkQueue) * c->opt.nq, hipMemcpyDeviceToHost));
     HCHK(hipMemcpyFromSymbol(st, HIP_SYMBOL(g_stamps), sizeof(st)));
     for (int k = 0; k < 4; ++k) out[k] = 0;
-    for (int p = 0; p < c->nq; ++p) {
+    for (int p = 0; p < c->opt.nq; ++p) {
         out[0] += q[p].item_used;
         out[1] += q[p].seg_used;
         out[2] += q[p].whole_used;
@@ -1245,7 +1079,7 @@ int hs_flush_ordinals(hs_ctx *c, void *hip_stream)
     LOCK(c);
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
     if (dev_enter(c, s) != HS_OK) return HS_EHIP;
-    c->ord_steps = c->ord_interval;  // due now
+    c->ord_steps = c->opt.ord_interval;  // due now
     const int rc = ord_sweep_if_due(c, s);
     if (rc != HS_OK) return rc;
     c->ord_steps = 0;  // no step of the new epoch has run yet

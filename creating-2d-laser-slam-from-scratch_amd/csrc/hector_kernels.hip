@@ -754,9 +754,6 @@ __device__ __forceinline__ void gn_step_reg(const float *__restrict__ cells, con
 // buffer, two barriers per chunk -- the first when the chain wave has finished chunk j - 1, the second when
 // the point waves have stored chunk j.  The adds are the same chain in the same order as
 // getCompleteHessianDerivs (OccGridMapUtil.h:94-126), so H / b are bit-identical to round 3's.
-constexpr int CW_PTS = MATCH_THREADS - 64;        // point threads
-constexpr int CW_NP = 6;                           // slots per point thread
-constexpr int CW_MAXN = CW_PTS * CW_NP;            // 1152 points in registers
 constexpr int CW_STRIDE = CW_PTS + 4;              // term-buffer row (words): 16-B aligned, row k on bank 4k
 constexpr int CW_BUF = 9 * CW_STRIDE;              // one chunk's terms
 // One term buffer (two barriers per chunk; 31.3 KB of LDS with REGS, 5 workgroups per CU), not two alternating
@@ -978,8 +975,6 @@ __device__ __forceinline__ void gn_step_cw(const float *__restrict__ cells, cons
     cs = sp[3];
     sn = sp[4];
 }
-
-constexpr int MATCH_REG_PTS = 5;  // points per thread kept in registers: scans of up to 1280 points
 
 // register budget of the reference-order register instances (gn_step_cw): waves per SIMD the compiler must fit
 // them into.  6 (default, round 6): 80 VGPRs; with the cache keys in registers and the gathers by LDS-DMA the
@@ -1220,9 +1215,6 @@ hs_match_kernel(FleetGeom geom, const float *__restrict__ cells, StreamState *__
 // Every ray starts at the common begin cell; a ray is stored as its end cell (packed y<<16 | x) or
 // RAY_INVALID when updateByScan would skip it (begin == end :157, or begin/end outside :226-238).
 constexpr unsigned RAY_INVALID = 0xFFFFFFFFu;
-// waves per hs_update_kernel workgroup: 256 threads, 64 x 32-cell LDS tiles, 8 workgroups per CU
-constexpr int UPD_WAVES = 4;
-constexpr int UPD_THREADS = 64 * UPD_WAVES;
 // two LDS words per tile cell, both updated with blind atomicMin (no read-modify-write chain):
 //   first_hit[c]  = smallest beam whose end cell is c      (NONE if none)
 //   first_free[c] = smallest beam that frees c            (NONE if none)
@@ -1383,7 +1375,6 @@ __device__ __forceinline__ bool walk_range(const RayWalk &w, int A0, int A1, int
 // This equals running bresenhamCellFree / bresenhamCellOcc (:302-330) beam by beam.
 constexpr unsigned W_NONE_ = 0xFFFFFFFFu;
 constexpr int BIN_THREADS = 256;
-constexpr int MAX_BIN_TILES = 1024;  // per level; larger bounding boxes use a WHOLE item
 constexpr int ITEM_TILE = 0, ITEM_WHOLE = 1;
 
 // Enumerate the tiles crossed by steps 0..da of a walk: f(tile_x, tile_y, lo, hi).
@@ -1831,18 +1822,12 @@ hs_tile_kernel(FleetGeom geom, float *__restrict__ cells, const StreamState *__r
 // Fan groups: beams b with the same b / 64 (one wave's lanes in one pass) share a bounding box
 // (origin + their end cells, computed once); a tile outside a group's box is skipped by the whole
 // wave with one scalar test.  Laser scans are angle-ordered, so a group is a narrow fan.
-// LDS words per tile row: 16-B rows (the apply reads and restores a quad's marks as one uint4) whose
+// LDS words per tile row (UPD_STRIDE, hector_internal.h): 16-B rows (the apply reads and restores a quad's marks as one uint4) whose
 // stride is not a multiple of 32 banks.  (67, odd, spreads a column of cells over all 32 banks of an
 // atomic's lane group instead of 8, but the raster's conflicts are mostly lanes on the SAME word, which
 // no stride changes -- tools/lds_sim.py: 2 % fewer raster LDS cycles -- and the unaligned quads cost the
 // apply more: measured 0.005 ms slower.)
-constexpr int UPD_STRIDE = 68;
 constexpr int UPD_MINB = 8;  // __launch_bounds__ minimum: 8 waves per SIMD, which caps the VGPRs at 64 (full occupancy)
-constexpr int UPD_TH = 8 * UPD_WAVES;                 // LDS tile height: every thread owns two quads of a tile
-// (64-row LDS tiles over two storage tiles, with 8 waves, were measured and not kept:
-// profiles/r07/retired_build_variants.md; the ordinal plane's offsets below assume one storage tile)
-static_assert(UPD_TH == TILE_H, "an LDS tile is one storage tile");
-constexpr int UPD_TILE_WORDS = UPD_TH * UPD_STRIDE;   // one LDS mark array
 // r * UPD_STRIDE for a tile row r in [0, UPD_TH): the mask shows the compiler a 16-bit operand, so it
 // selects the full-rate v_mul_u32_u24 (r * 68 of an int of unknown range, and even __mul24 or a
 // shift-and-add it recombined, became a quarter-rate v_mul_lo_u32)
@@ -1913,11 +1898,6 @@ __device__ __forceinline__ float apply_cell(float l, unsigned odd, unsigned hit,
 // inside its storage tile
 __device__ __forceinline__ int upd_off(int row, int c4) { return tile_cell(c4, row); }
 
-constexpr int UPD_HIT_WORDS = UPD_TH * (TILE / 32);                  // one hit bit per tile cell
-constexpr int UPD_MARK_WORDS = (UPD_TILE_WORDS + UPD_HIT_WORDS + 3) & ~3;
-
-constexpr int UPD_FIXED_WORDS = 2 * UPD_MARK_WORDS + 4;  // two mark buffers + 4 spare words; then rays, fan-group boxes
-
 // the free mark of one raster step: blind LDS atomicMin of the event code
 __device__ __forceinline__ void upd_mark(unsigned *p, unsigned ev) { atomicMin(p, ev); }
 // 32-bit LDS byte address of an LDS pointer, and back (the walk carries addresses in packed registers)
@@ -1942,11 +1922,6 @@ __device__ __forceinline__ int fan_beam(int b0, int lane)  // b0 = 256 G + 64 w
 {
     return b0 + 2 * (lane & 31) + (lane >> 5);
 }
-__host__ __device__ constexpr int fan_groups(int max_points)
-{
-    return ((max_points + UPD_THREADS - 1) / UPD_THREADS) * UPD_WAVES;
-}
-constexpr int UPD_GROUP_WORDS = 4;  // LDS words per fan group: its bounding box
 
 // Grid: for level l, upd_parts[l] x count blocks (level-major, then part, then stream); part p of a
 // level draws the tiles t = p, p + parts, ... of the scan's tile box (t row-major over the box).
@@ -1955,7 +1930,6 @@ constexpr int UPD_GROUP_WORDS = 4;  // LDS words per fan group: its bounding box
 // at 1081 beams, 8 instead of 7 workgroups per CU (the kernel's VGPRs allow 8).  RREG = 0: rays in LDS.
 // The rays are five named registers picked by selects on the wave-uniform fan-group index (an array
 // or a struct indexed by it ends up in scratch).
-constexpr int UPD_RREG = (1280 + UPD_THREADS - 1) / UPD_THREADS;  // scans of <= 1280 points
 static_assert(UPD_RREG <= 5, "five ray registers at most");
 template <int RREG>
 __global__ void __launch_bounds__(UPD_THREADS, UPD_MINB)
@@ -2256,7 +2230,7 @@ hs_update_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__restr
                     // incremental walk, f = da - 1 - error_b in [0, da) (backwards: g = error_b), packed with
                     // the LDS byte address of the step's mark word into ONE register, V = f << 18 | address
                     // (LDS addresses < 2^18, f < da <= 2^14: the host sends larger maps to the binned kernels,
-                    // upd_single_ok): the subtraction of db << 18 borrows exactly when
+                    // plan_step): the subtraction of db << 18 borrows exactly when
                     // f < db -- the minor axis steps -- and one select + add then moves both fields.  Three
                     // VALU per step plus the address mask, instead of five.
                     const int dab1 = w.sa > 0 ? 4 * la : -4 * la;              // (no quarter-rate 32-bit multiply)
@@ -2388,7 +2362,7 @@ hs_update_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__restr
 }
 
 // ------------------------------- k2 (opt-in, SLAM2D_UPD_KERNEL=ring): ring-ordered grid update with ray cursors
-// (the default update is the clip kernel hs_update_kernel above; hector_capi.hip upd_ring_ok)
+// (the default update is the clip kernel hs_update_kernel above; hector_internal.h plan_step)
 // The same once-per-scan update as hs_update_kernel (tiles of 64 x UPD_TH cells, LDS event words + hit
 // bits, the two-stage raster / apply pipeline, fan groups culled per tile with one ballot), with the
 // per-(tile, ray) clip replaced by a cursor per ray.
@@ -2407,23 +2381,10 @@ hs_update_kernel(FleetGeom geom, float *__restrict__ cells, StreamState *__restr
 // Per ray two registers (scans of <= RING_GROUPS * 256 points; larger scans use hs_update_kernel<0>):
 //   consts  = da | db << 14 | (x step < 0) << 28 | (y step < 0) << 29 | x major << 30   (0: no ray)
 //   cursor  = i | q << 16: step i is next, q = its minor steps (i > da: the ray is done)
-// (da, db < 2^14: maps of at most 16384 cells per side, upd_ring_ok).
-// LDS tile height of the ring kernel: one storage tile, 256-thread workgroups (64 rows with 512-thread workgroups
-// were measured and not kept: profiles/r07/retired_build_variants.md; the apply's ordinal offsets assume one
-// storage tile per LDS tile)
-constexpr int RTH = TILE_H;
-constexpr int RTHREADS = 256;
-constexpr int RWAVES = RTHREADS / 64;
-static_assert(RTH == TILE_H, "a ring tile is one storage tile");
-constexpr int RTILE_WORDS = RTH * UPD_STRIDE;                       // one LDS mark array
-constexpr int RHIT_WORDS = RTH * (TILE / 32);                       // one hit bit per tile cell
-constexpr int RMARK_WORDS = (RTILE_WORDS + RHIT_WORDS + 3) & ~3;
-constexpr int RFIXED_WORDS = 2 * RMARK_WORDS + 4;                  // two mark buffers + 4 spare words; then fan boxes
+// (da, db < 2^14: maps of at most 16384 cells per side, plan_step).
+// (RTH, RTHREADS, RWAVES, the mark-buffer sizes, RING_GROUPS and ring_shmem_words: hector_internal.h)
 constexpr int RQUADS = TILE * RTH / 4 / RTHREADS;                   // apply quads per thread per tile
 constexpr unsigned long long RGROUP_MASK = 0x1111111111111111ull;
-constexpr int RING_GROUPS = (5 * 256 + RTHREADS - 1) / RTHREADS;    // fan groups per lane: scans of <= 1280 points
-__host__ __device__ constexpr int ring_fan_groups(int max_points) { return ((max_points + RTHREADS - 1) / RTHREADS) * RWAVES; }
-__host__ __device__ constexpr int ring_shmem_words(int max_points) { return RFIXED_WORDS + UPD_GROUP_WORDS * ring_fan_groups(max_points); }
 // word offset of the quad at (c4, row) of the LDS tile in the level's tiled storage (see upd_off)
 __device__ __forceinline__ int ring_off(int row, int c4) { return tile_cell(c4, row); }
 constexpr unsigned CUR_DONE = 0xFFFFu;

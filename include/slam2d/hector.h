@@ -56,6 +56,7 @@ const char *hs_last_error(void);
  * map_resolution/map_size/start/levels are the ROS params map_resolution, map_size, map_start_x/y,
  * map_multi_res_levels (hector_slam.cc:138-142).  max_points bounds the scan size (>= 1). */
 /* Limits: map sizes <= 32768 cells per side, 1 <= max_points <= 65535. */
+/* hs_create reads the SLAM2D_* environment knobs named below, and the others, once: DESIGN.md section 5, "Host knobs". */
 int hs_create(hs_ctx **out, int num_streams, float map_resolution, int map_size_x, int map_size_y,
               float map_start_x, float map_start_y, int levels, int max_points);
 /* ~HectorSlamProcessor (HectorSlamProcessor.h:70-73) */

@@ -8,8 +8,9 @@ asserts the resulting begin and end cells with the plain statement (tests/ref/he
 derives them by a formula of its own.
 
 A Path is a way through the host's launch logic: environment variables read at hs_create and the max_points that
-selects the kernel instance.  admits() restates the host's limits (hector_capi.hip upd_single_ok / upd_ring_ok /
-upd_rays_in_regs); parts() restates upd_split and the SLAM2D_UPD_PARTS parse.
+selects the kernel instance.  admits() and shmem_bytes() restate the host's limits (hector_internal.h plan_step);
+parts() restates upd_split and the SLAM2D_UPD_PARTS parse (parse_options).  tests/test_hector_launch_cpu.py holds all
+of them, and the constants below, to the library's own header on the CPU.
 
 replay(case) runs the oracle and the plain statement side by side, update by update, records every difference and
 returns the facts per update and level (cached: the CPU tests share one replay per case).
@@ -27,7 +28,7 @@ RES = 0.05
 FREE, OCC = 0.4, 0.9
 TILE, TILE_H = 64, 32
 NAN, INF = float("nan"), float("inf")
-# csrc/hector_kernels.hip: UPD_THREADS, UPD_STRIDE, UPD_TH, UPD_HIT_WORDS, UPD_MARK_WORDS, UPD_FIXED_WORDS, UPD_GROUP_WORDS
+# csrc/hector_internal.h: UPD_THREADS, UPD_STRIDE, UPD_TH, UPD_HIT_WORDS, UPD_MARK_WORDS, UPD_FIXED_WORDS, UPD_GROUP_WORDS
 UPD_THREADS = 256
 UPD_MARK_WORDS = (32 * 68 + 32 * 2 + 3) & ~3
 UPD_FIXED_WORDS = 2 * UPD_MARK_WORDS + 4
@@ -372,7 +373,7 @@ class Path:
         return max(n, REG_POINTS + 1) if self.inst == "lds" else n
 
     def shmem_bytes(self, case):
-        """upd_shmem_bytes: the mark buffers, the rays (LDS instance) and a box per fan group."""
+        """plan_step's shmem: the mark buffers, the rays (LDS instance) and a box per fan group."""
         mp = self.max_points(case)
         rays = 0 if mp <= REG_POINTS else (mp + 3) & ~3
         return 4 * (UPD_FIXED_WORDS + rays + 4 * (-(-mp // UPD_THREADS) * 4))

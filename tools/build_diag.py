@@ -101,10 +101,10 @@ PATCHES = {
     "nowalk": [(K, "                    if ((int)!met | (int)(lo_i > hi_i)) continue;\n                    anyv = 1u;\n",
                 "                    if ((int)!met | (int)(lo_i > hi_i)) continue;\n                    anyv = 1u;\n                    continue;\n")],
     "ktnorender": [("karto_kernels.hip", "kt_render_items_dw(tileb, sitem, c0, c1,", "kt_render_items_dw(tileb, sitem, c0, c0,")],
-    "lds6": [("hector_capi.hip", "UPD_GROUP_WORDS * (size_t)fan_groups(c->max_points));\n}",
-              "UPD_GROUP_WORDS * (size_t)fan_groups(c->max_points) + 2100);\n}")],
-    "lds4": [("hector_capi.hip", "UPD_GROUP_WORDS * (size_t)fan_groups(c->max_points));\n}",
-              "UPD_GROUP_WORDS * (size_t)fan_groups(c->max_points) + 5430);\n}")],
+    "lds6": [("hector_internal.h", "UPD_GROUP_WORDS * (size_t)fan_groups(sh.max_points);\n",
+              "UPD_GROUP_WORDS * (size_t)fan_groups(sh.max_points) + 2100;\n")],
+    "lds4": [("hector_internal.h", "UPD_GROUP_WORDS * (size_t)fan_groups(sh.max_points);\n",
+              "UPD_GROUP_WORDS * (size_t)fan_groups(sh.max_points) + 5430;\n")],
     "ktnomerge": [("karto_kernels.hip", "    for (int t0 = lane; t0 < nw; t0 += 64 * 8) {\n        unsigned long long want[8], old[8];",
                    "    if (nw > 0) return true;\n    for (int t0 = lane; t0 < nw; t0 += 64 * 8) {\n        unsigned long long want[8], old[8];")],
     "ktstore": [("karto_kernels.hip", "                old[u] = atomicCAS(gw + wbase + r * wsw + q, 0ull, want[u]);",
@@ -187,11 +187,11 @@ PATCHES = {
               "            lds_barrier();\n            if (j == 0) mk_t1 = __builtin_amdgcn_s_memtime();\n            if (lane < 9) run = seq_chain_t<CW_STRIDE>("),
              (K, "n - j * CW_PTS), run);\n        }\n    }\n    float *sp = s_pose[parity];\n    if (wave == cw) {\n        float s[9], H[9];",
               "n - j * CW_PTS), run);\n        }\n        mk_t2 = __builtin_amdgcn_s_memtime();\n    }\n    float *sp = s_pose[parity];\n    if (wave == cw) {\n        float s[9], H[9];"),
-             (K, "    __syncthreads();\n    // (H stays in s_pose, read once at the level's end)\n    est[0] = sp[0];\n    est[1] = sp[1];\n    est[2] = sp[2];\n    cs = sp[3];\n    sn = sp[4];\n}\n\nconstexpr int MATCH_REG_PTS",
+             (K, "    __syncthreads();\n    // (H stays in s_pose, read once at the level's end)\n    est[0] = sp[0];\n    est[1] = sp[1];\n    est[2] = sp[2];\n    cs = sp[3];\n    sn = sp[4];\n}\n\n// register budget",
               "    if (wave == cw && lane == 0) {\n        const unsigned long long mk_t3 = __builtin_amdgcn_s_memtime();\n"
               "        s_mk[0] += mk_t1 - mk_t0; s_mk[1] += mk_t2 - mk_t1; s_mk[2] += mk_t3 - mk_t2;\n    }\n"
               "    if (wave != cw && pt == 0) { s_mk[4] += mk_pa - mk_t0; s_mk[5] += mk_pb - mk_pa; s_mk[6] += mk_pc - mk_pb; if (mk_big) s_mk[7] += mk_pb - mk_pa; }\n"
-              "    __syncthreads();\n    // (H stays in s_pose, read once at the level's end)\n    est[0] = sp[0];\n    est[1] = sp[1];\n    est[2] = sp[2];\n    cs = sp[3];\n    sn = sp[4];\n}\n\nconstexpr int MATCH_REG_PTS"),
+              "    __syncthreads();\n    // (H stays in s_pose, read once at the level's end)\n    est[0] = sp[0];\n    est[1] = sp[1];\n    est[2] = sp[2];\n    cs = sp[3];\n    sn = sp[4];\n}\n\n// register budget"),
              (K, "        if (first) {\n            // a level's first step",
               "        mk_pa = __builtin_amdgcn_s_memtime();\n        if (first) {\n            // a level's first step"),
              (K, "        lds_barrier();\n    }\n    if (wave != cw) {\n        // chunk j = slot j",
