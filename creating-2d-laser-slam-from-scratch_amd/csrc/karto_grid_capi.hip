@@ -11,7 +11,9 @@
 #include <string>
 #include <vector>
 
+#include "host_timing.h"
 #include "karto_grid_kernels.hip"
+#include "karto_internal.h"  // kg_parse_options, kg_split_rule
 
 using namespace s2d;
 
@@ -38,11 +40,11 @@ double g_round(double v) { return v >= 0.0 ? std::floor(v + 0.5) : std::ceil(v -
 
 constexpr size_t KG_MAX_CELLS = (size_t)1 << 28;
 constexpr double KG_MAX_REACH = 1048576.0;  // range_threshold / resolution, cells
-constexpr int KG_MAX_SPLIT = 32;
 
 enum { G_BBOX, G_REDUCE, G_RAYS, G_TRACE, G_UPDATE, G_NUM };
 const char *const g_names[G_NUM] = {"kg_bbox_kernel", "kg_bbox_reduce_kernel", "kg_rays_kernel", "kg_trace_kernel",
                                     "kg_update_kernel"};
+static_assert(G_NUM <= KernelTimer::MAX_KERNELS, "the timer's accumulators");
 }  // namespace
 
 struct kg_ctx {
@@ -60,65 +62,12 @@ struct kg_ctx {
     int8_t *d_ros = nullptr;
     hipStream_t stream = nullptr, last = nullptr;
     std::mutex mu;
-    bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_free;
-    std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> ev_used;
-    double acc_ms[G_NUM] = {};
-    int64_t acc_n[G_NUM] = {};
+    KernelTimer timer;
 };
 
 namespace {
 
-int kg_begin_event(kg_ctx *c, hipStream_t s, std::pair<hipEvent_t, hipEvent_t> &ev)
-{
-    if (!c->timing) return KG_OK;
-    if (!c->ev_free.empty()) {
-        ev = c->ev_free.back();
-        c->ev_free.pop_back();
-    } else {
-        GCHK(hipEventCreate(&ev.first));
-        GCHK(hipEventCreate(&ev.second));
-    }
-    GCHK(hipEventRecord(ev.first, s));
-    return KG_OK;
-}
-
-int kg_end_event(kg_ctx *c, hipStream_t s, int which, std::pair<hipEvent_t, hipEvent_t> &ev)
-{
-    GCHK(hipGetLastError());
-    if (!c->timing) return KG_OK;
-    GCHK(hipEventRecord(ev.second, s));
-    c->ev_used.push_back({which, ev});
-    return KG_OK;
-}
-
-#define KG_LAUNCH(which, ...)                    \
-    do {                                         \
-        std::pair<hipEvent_t, hipEvent_t> _ev{}; \
-        int _rc = kg_begin_event(c, s, _ev);     \
-        if (_rc != KG_OK) return _rc;            \
-        hipLaunchKernelGGL(__VA_ARGS__);         \
-        _rc = kg_end_event(c, s, which, _ev);    \
-        if (_rc != KG_OK) return _rc;            \
-    } while (0)
-
-// Workgroups per tile.  One owner per tile (plain stores, no memset) as soon as the tiles alone fill every
-// CU's four resident workgroups (the tile's 33 KB of LDS); below that the tiles' scan lists are split so that
-// about 4 * CUs workgroups run, never finer than 32 scans per workgroup.  The split is rounded up to 1, 2, 4 or
-// a multiple of 8: workgroups go to the 8 XCDs round-robin and the part is blockIdx % split, so each XCD's L2
-// then serves the rays of split / 8 parts only -- the supposed cause of what was measured, 15 parts 2.58 ms and
-// 16 parts 1.73 ms per rebuild (profiles/r07/karto_grid.md).
-int kg_split_rule(const kg_ctx *c, int ntiles, int count)
-{
-    if (c->force_split > 0) return std::min(c->force_split, KG_MAX_SPLIT);
-    const int want = 4 * c->num_cus;
-    if (ntiles >= want) return 1;
-    int split = (want + ntiles - 1) / ntiles;
-    split = std::max(1, std::min(split, (count + 31) / 32));
-    if (split > 4) split = (split + 7) & ~7;
-    else if (split == 3) split = 4;
-    return std::min(split, KG_MAX_SPLIT);
-}
+#define KG_LAUNCH(which, ...) S2D_TIMED_LAUNCH(c->timer, gfail, KG_EHIP, s, which, __VA_ARGS__)
 
 int kg_run(kg_ctx *c, int count, const double *d_ranges, const double *d_poses, kg_info *info, hipStream_t s)
 {
@@ -156,7 +105,7 @@ int kg_run(kg_ctx *c, int count, const double *d_ranges, const double *d_poses, 
     g.tiles_x = (g.width + KG_TILE - 1) / KG_TILE;
     g.tiles_y = (g.height + KG_TILE - 1) / KG_TILE;
     const int ntiles = g.tiles_x * g.tiles_y;
-    g.split = kg_split_rule(c, ntiles, count);
+    g.split = kg_split_rule(c->force_split, c->num_cus, ntiles, count);
     const size_t cells = (size_t)g.width * g.height;
 
     KG_LAUNCH(G_RAYS, kg_rays_kernel, dim3(count), dim3(KG_THREADS), 0, s, g, d_ranges, d_poses, c->d_rays,
@@ -202,6 +151,9 @@ int kg_create(kg_ctx **out, const kt_laser *L, const kg_params *p, int max_scans
         return gfail(KG_EINVAL, "range_threshold must be > 0 and at most 2^20 cells long");
     if (max_scans < 1 || max_cells < 1 || max_cells > KG_MAX_CELLS)
         return gfail(KG_EINVAL, "need max_scans >= 1 and 1 <= max_cells <= 2^28");
+    int force_split = 0;
+    if (const char *refused = kg_parse_options(force_split, [](const char *knob) -> const char * { return getenv(knob); }))
+        return gfail(KG_EINVAL, refused);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return gfail(KG_ENODEV, "no HIP device");
     int dev = 0;
@@ -212,7 +164,7 @@ int kg_create(kg_ctx **out, const kt_laser *L, const kg_params *p, int max_scans
     c->max_scans = max_scans;
     c->max_cells = max_cells;
     c->num_cus = std::max(1, prop.multiProcessorCount);
-    if (const char *e = getenv("SLAM2D_KG_SPLIT")) c->force_split = atoi(e);
+    c->force_split = force_split;
     KgGeom &g = c->g;
     g.min_angle = L->minimum_angle;
     g.ang_res = L->angular_resolution;
@@ -256,14 +208,7 @@ int kg_destroy(kg_ctx *c)
                     c->d_pass,   c->d_hits,  c->d_state, c->d_ros};
     for (void *b : bufs) hipFree(b);
     if (c->h_box) hipHostFree(c->h_box);
-    for (auto &p : c->ev_free) {
-        hipEventDestroy(p.first);
-        hipEventDestroy(p.second);
-    }
-    for (auto &p : c->ev_used) {
-        hipEventDestroy(p.second.first);
-        hipEventDestroy(p.second.second);
-    }
+    c->timer.destroy();
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
     return KG_OK;
@@ -332,7 +277,7 @@ int kg_device_planes(kg_ctx *c, const uint8_t **d_state, const int8_t **d_ros, c
 int kg_set_timing(kg_ctx *c, int enable)
 {
     if (!c) return gfail(KG_EINVAL, "ctx is NULL");
-    c->timing = enable != 0;
+    c->timer.on = enable != 0;
     return KG_OK;
 }
 
@@ -343,22 +288,7 @@ int kg_get_kernel_times(kg_ctx *c, double *ms_out, int64_t *launches_out, int re
 {
     if (!c) return gfail(KG_EINVAL, "ctx is NULL");
     GCHK(hipDeviceSynchronize());
-    for (auto &u : c->ev_used) {
-        float ms = 0;
-        GCHK(hipEventElapsedTime(&ms, u.second.first, u.second.second));
-        c->acc_ms[u.first] += ms;
-        c->acc_n[u.first] += 1;
-        c->ev_free.push_back(u.second);
-    }
-    c->ev_used.clear();
-    for (int i = 0; i < G_NUM; ++i) {
-        if (ms_out) ms_out[i] = c->acc_ms[i];
-        if (launches_out) launches_out[i] = c->acc_n[i];
-        if (reset) {
-            c->acc_ms[i] = 0;
-            c->acc_n[i] = 0;
-        }
-    }
+    GCHK(c->timer.collect(ms_out, launches_out, reset, G_NUM));
     return KG_OK;
 }
 

@@ -37,13 +37,10 @@
 
 #include "../../include/slam2d/karto.h"
 #include "detmath.h"
+#include "karto_internal.h"  // KtGeom, KT_THREADS and the other sizes the host's launch plan shares
 
 namespace s2d {
 
-constexpr int KT_THREADS = 256;
-constexpr int KT_MAX_READINGS = 4096;
-constexpr int KT_FINE_MAX_ANG = 64;
-constexpr int KT_MAX_NXY = 1024;  // coarse positions per axis
 constexpr int KT_SEL_ITEMS = 16;
 constexpr int KT_INVALID = INT_MIN;  // INVALID_SCAN: any position index + this is negative -> skipped
 constexpr double KT_PI = 3.14159265358979323846;
@@ -51,31 +48,6 @@ constexpr double KT_2PI = 6.28318530717958647692;
 constexpr double KT_TOL = 1e-06;
 constexpr double KT_MAX_VARIANCE = 500.0;
 constexpr double KT_GAIN = 0.2;  // DISTANCE_PENALTY_GAIN == ANGLE_PENALTY_GAIN (Mapper.cpp:37-38)
-constexpr int KT_OCC = 100;
-
-// Host-computed geometry of one ScanMatcher (ScanMatcher::Create + CorrelateScan's search spaces).
-struct KtGeom {
-    double scale, res;                 // 1 / resolution, GetResolution() = 1 / scale
-    int grid_size, border, width, height, ws, data_size;
-    int side, probs_ws, half, ksize;
-    int n;                             // readings per scan
-    int nxy;                           // coarse positions per axis
-    int ctx, cty, clw;                 // coarse position tiles along x / y; log2 of gather lanes per tile row
-    int npass;                         // 1, or 4 with response expansion
-    int nang[4];
-    double aoff[4];                    // coarse angle offset per pass
-    double coff, cres;                 // coarse search offset / resolution
-    double foff;                       // fine search offset (resolution = res)
-    int fn, fnang;                     // fine positions per axis, fine angles
-    double faoff, fares;               // fine angle offset / resolution
-    double min_angle, ang_res, min_range, range_thr;
-    double dvp, avp, mdp, map_;        // penalties
-    double cares;                      // coarse angle resolution
-    int use_expansion;
-    int max_poses;
-    size_t grid_stride;                // bytes per match slot grid
-    int tiles_x, tiles_y, ntiles;      // 64 x 64-cell tiles of the grid (kt_addscans_kernel)
-};
 
 struct KtPool {
     const double *ranges;  // [S][n]
@@ -521,12 +493,9 @@ __device__ unsigned long long kt_diag[65536 * 8];
 #else
 #define KT_STAMP(i) do { } while (0)
 #endif
-constexpr int KT_AS_WAVES = 8;
 constexpr int KT_AS_ITEMS = 15360;     // tile-sorted footprint items per pass (60 KB of LDS)
 constexpr int KT_AS_MARGIN = 16;       // LDS tile margin (footprints of kernel half <= 8 stay inside)
 constexpr int KT_AS_TW = 64 + 2 * KT_AS_MARGIN;
-constexpr int KT_AS_MAX_TILES = 2048;  // tiles per grid (e.g. 2896 x 2896 cells)
-constexpr int KT_AS_MAX_BASE = 1024;
 constexpr int KT_AS_CLASSES = 12;  // tile size classes of the render order
 
 __device__ __forceinline__ int kt_size_class(int c)  // 0 for c >= 2^11, 11 for c == 1
@@ -1429,7 +1398,6 @@ kt_select_kernel(KtGeom g, KtState *st, const double *__restrict__ resp, unsigne
 // atomic add per wave (integer sums, order-free): no barrier between angles, and four points' offsets
 // and gathers (36 bytes) in flight per lane instead of one point's.
 // =================================================================================================
-constexpr int KT_FINE_THREADS = KT_THREADS;  // 1024 threads (4 waves per SIMD) measured slower
 constexpr int KT_FINE_PPT = 16;              // points per thread held in registers: n <= 4096 = 16 * 256
 __device__ __forceinline__ int kt_offset(const KtGeom &g, double cs, double sn, double2 l, double gox, double goy)
 {

@@ -126,7 +126,9 @@ int kt_match_batch_device(kt_ctx *ctx, int count, const int *d_query, const int 
  * with MAX over the ranks (RCCL over xGMI), then phase 2 imports it and finishes the reference
  * sequence: best, tie average in pose order, positional covariance (Mapper.cpp:427-523), fine match.
  * Every rank ends with the identical result, bit-equal to kt_match_batch_device.  Requires
- * count <= the context's slots and no response expansion (KT_EINVAL otherwise). */
+ * count <= the context's slots and no response expansion (KT_EINVAL otherwise).  Calls come in matching
+ * pairs: an end call follows the begin call of the same batch on the same context with the same count and
+ * base-scan arrays (it clears the grids the way the begin call, by its count, built them). */
 size_t kt_window_exchange_words(kt_ctx *ctx);
 int kt_match_sharded_begin_device(kt_ctx *ctx, int count, const int *d_query, const int *d_base_begin,
                                   const int *d_base_index, int do_penalize, int shard, int nshards,
