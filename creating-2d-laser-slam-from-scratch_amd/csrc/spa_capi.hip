@@ -38,6 +38,7 @@ int sfail(int code, const char *what, hipError_t e = hipSuccess)
 constexpr int SPA_MAX_GRAPHS = 1 << 16;
 constexpr int SPA_MAX_NODES = 1 << 20;
 constexpr int SPA_MAX_CONS = 1 << 22;
+constexpr int SPA_MAX_FACTOR_BLOCKS = 1 << 27;
 }  // namespace
 
 struct spa_ctx {
@@ -51,7 +52,7 @@ struct spa_ctx {
     int2 *d_con_nd = nullptr, *d_nbr = nullptr;
     double *d_con_mean = nullptr, *d_con_prec = nullptr;
     int *d_inc_off = nullptr, *d_inc = nullptr, *d_nbr_off = nullptr, *d_pair_off = nullptr, *d_pair_con = nullptr;
-    size_t scratch_bytes = 0;
+    size_t scratch_bytes = 0, fac_bytes = 0, fidx_bytes = 0;
     hipStream_t stream = nullptr, last = nullptr;
     hipEvent_t ev_last = nullptr;
     std::mutex mu;
@@ -116,6 +117,8 @@ int check_params(const spa_params *p)
         return sfail(SPA_EINVAL, "niter * max_cg_iters exceeds SPA_MAX_ITER_PRODUCT");
     if (!(p->lambda > 0) || !std::isfinite(p->lambda)) return sfail(SPA_EINVAL, "lambda must be > 0 and finite");
     if (!(p->init_tol >= 0)) return sfail(SPA_EINVAL, "init_tol must be >= 0");
+    if (p->solver != SPA_SOLVER_PCG && p->solver != SPA_SOLVER_CHOLESKY)
+        return sfail(SPA_EINVAL, "solver must be SPA_SOLVER_PCG or SPA_SOLVER_CHOLESKY");
     return SPA_OK;
 }
 
@@ -129,7 +132,12 @@ int run(spa_ctx *c, int g_first, int count, const spa_params *p, hipStream_t s)
         if (c->dirty[g] && (rc = upload_graph(c, g)) != SPA_OK) return rc;
     // order after the context's previous device work, whichever stream it ran on (DESIGN.md "Streams")
     SCHK(hipStreamWaitEvent(s, c->ev_last, 0));
-    hipLaunchKernelGGL(spa_solve_kernel, dim3((unsigned)count), dim3(SPA_THREADS), 0, s, c->dev, g_first, *p);
+    if (p->solver == SPA_SOLVER_CHOLESKY)
+        hipLaunchKernelGGL(spa_solve_kernel<SPA_SOLVER_CHOLESKY>, dim3((unsigned)count), dim3(SPA_THREADS), 0, s, c->dev,
+                           g_first, *p);
+    else
+        hipLaunchKernelGGL(spa_solve_kernel<SPA_SOLVER_PCG>, dim3((unsigned)count), dim3(SPA_THREADS), 0, s, c->dev,
+                           g_first, *p);
     SCHK(hipGetLastError());
     SCHK(hipEventRecord(c->ev_last, s));
     c->last = s;
@@ -141,7 +149,7 @@ int run(spa_ctx *c, int g_first, int count, const spa_params *p, hipStream_t s)
 extern "C" {
 
 const char *spa_last_error(void) { return spa_err.c_str(); }
-const char *spa_version(void) { return "slam2d-spa 1 (gfx950, block-Jacobi PCG)"; }
+const char *spa_version(void) { return "slam2d-spa 2 (gfx950, block-Jacobi PCG, envelope Cholesky)"; }
 
 void spa_default_params(spa_params *p)
 {
@@ -156,8 +164,15 @@ void spa_default_params(spa_params *p)
 
 int spa_create(spa_ctx **out, int max_graphs, int max_nodes, int max_constraints)
 {
+    return spa_create_ex(out, max_graphs, max_nodes, max_constraints, 0);
+}
+
+int spa_create_ex(spa_ctx **out, int max_graphs, int max_nodes, int max_constraints, int max_factor_blocks)
+{
     if (!out) return sfail(SPA_EINVAL, "out is NULL");
     *out = nullptr;
+    if (max_factor_blocks < 0 || max_factor_blocks > SPA_MAX_FACTOR_BLOCKS)
+        return sfail(SPA_EINVAL, "need 0 <= max_factor_blocks <= 2^27");
     if (max_graphs < 1 || max_graphs > SPA_MAX_GRAPHS || max_nodes < 1 || max_nodes > SPA_MAX_NODES ||
         max_constraints < 1 || max_constraints > SPA_MAX_CONS)
         return sfail(SPA_EINVAL, "need 1 <= max_graphs <= 2^16, 1 <= max_nodes <= 2^20, 1 <= max_constraints <= 2^22");
@@ -173,6 +188,8 @@ int spa_create(spa_ctx **out, int max_graphs, int max_nodes, int max_constraints
     c->n_fixed.assign((size_t)max_graphs, SPA_FIXED_FROM_PARAMS);
     const size_t G = (size_t)max_graphs, N = (size_t)max_nodes, M = (size_t)max_constraints;
     c->scratch_bytes = sizeof(double) * G * spa_scratch_doubles(max_nodes, max_constraints);
+    c->fac_bytes = sizeof(double) * G * (size_t)max_factor_blocks * 9;
+    c->fidx_bytes = sizeof(int) * G * spa_fidx_ints(max_nodes);
     hipError_t e;
     if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamDefault)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&c->ev_last, hipEventDisableTiming)) != hipSuccess) {
@@ -191,12 +208,15 @@ int spa_create(spa_ctx **out, int max_graphs, int max_nodes, int max_constraints
         (e = hipMalloc(&c->d_pair_off, sizeof(int) * G * (M + 1))) != hipSuccess ||
         (e = hipMalloc(&c->d_pair_con, sizeof(int) * G * M)) != hipSuccess ||
         (e = hipMalloc(&c->dev.scratch, c->scratch_bytes)) != hipSuccess ||
+        (c->fac_bytes > 0 && (e = hipMalloc(&c->dev.fac, c->fac_bytes)) != hipSuccess) ||
+        (e = hipMalloc(&c->dev.fidx, c->fidx_bytes)) != hipSuccess ||
         (e = hipMalloc(&c->dev.stats, sizeof(spa_stats) * G)) != hipSuccess) {
         spa_destroy(c);
         return sfail(SPA_ENOMEM, "hipMalloc", e);
     }
     c->dev.max_nodes = max_nodes;
     c->dev.max_cons = max_constraints;
+    c->dev.max_fac = max_factor_blocks;
     c->dev.hdr = c->d_hdr;
     c->dev.con_nd = c->d_con_nd;
     c->dev.con_mean = c->d_con_mean;
@@ -228,7 +248,8 @@ int spa_destroy(spa_ctx *c)
     if (c->last) hipStreamSynchronize(c->last);
     if (c->stream) hipStreamSynchronize(c->stream);
     void *bufs[] = {c->d_hdr, c->dev.poses, c->d_con_nd, c->d_con_mean, c->d_con_prec, c->d_inc_off, c->d_inc,
-                    c->d_nbr_off, c->d_nbr, c->d_pair_off, c->d_pair_con, c->dev.scratch, c->dev.stats};
+                    c->d_nbr_off, c->d_nbr, c->d_pair_off, c->d_pair_con, c->dev.scratch, c->dev.stats, c->dev.fac,
+                    c->dev.fidx};
     for (void *b : bufs)
         if (b) hipFree(b);
     if (c->ev_last) hipEventDestroy(c->ev_last);
@@ -323,6 +344,18 @@ int spa_get_counts(spa_ctx *c, int g, int *n_nodes, int *n_cons)
     return SPA_OK;
 }
 
+int spa_envelope_blocks(spa_ctx *c, int g, int n_fixed, long long *blocks)
+{
+    int rc = check_graph(c, g);
+    if (rc != SPA_OK) return rc;
+    if (!blocks) return sfail(SPA_EINVAL, "blocks is NULL");
+    std::lock_guard<std::mutex> lock(c->mu);
+    SpaGraph &gr = c->graphs[g];
+    if (c->dirty[g]) gr.compile();  // the lists only; the upload stays with the next compute
+    *blocks = gr.envelope_blocks(n_fixed);
+    return SPA_OK;
+}
+
 int spa_compute_device(spa_ctx *c, int g_first, int count, const spa_params *params, void *hip_stream)
 {
     if (!c) return sfail(SPA_EINVAL, "ctx is NULL");
@@ -388,6 +421,8 @@ int spa_poison_scratch(spa_ctx *c, int byte)
     int rc = wait_last(c);
     if (rc != SPA_OK) return rc;
     SCHK(hipMemset(c->dev.scratch, byte, c->scratch_bytes));
+    if (c->fac_bytes > 0) SCHK(hipMemset(c->dev.fac, byte, c->fac_bytes));
+    SCHK(hipMemset(c->dev.fidx, byte, c->fidx_bytes));
     SCHK(hipDeviceSynchronize());
     return SPA_OK;
 }

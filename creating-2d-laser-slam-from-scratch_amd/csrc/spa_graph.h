@@ -103,6 +103,27 @@ struct SpaGraph {
         }
         for (int k = 0; k < n; ++k) nbr_off[(size_t)k + 1] += nbr_off[k];
     }
+
+    // The direct solve's envelope (spa.h "The direct solve"), from compile()'s neighbour lists: first[k] of node
+    // k >= n_fixed is the first entry >= n_fixed of its ascending neighbour list when that is < k, else k.
+    int envelope_first(int k, int n_fixed) const
+    {
+        for (int j = nbr_off[k]; j < nbr_off[(size_t)k + 1]; ++j) {
+            const int nb = nbr[j][0];
+            if (nb >= n_fixed) return nb < k ? nb : k;
+        }
+        return k;
+    }
+
+    // The envelope's 3 x 3 blocks: the sum over the free nodes of k - first[k] + 1; 0 when nothing is fixed (such
+    // a compute is refused).  n_fixed beyond the node count leaves no free node.
+    long long envelope_blocks(int n_fixed) const
+    {
+        if (n_fixed <= 0) return 0;
+        long long blocks = 0;
+        for (int k = n_fixed; k < n_nodes(); ++k) blocks += (long long)(k - envelope_first(k, n_fixed)) + 1;
+        return blocks;
+    }
 };
 
 }  // namespace s2d

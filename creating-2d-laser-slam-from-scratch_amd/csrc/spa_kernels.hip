@@ -1,5 +1,7 @@
 // spa_kernels.hip -- Karto's pose-graph optimiser on the device: SysSPA2d::doSPA in its block-Jacobi PCG mode
-// (lesson6/lib/sparse_bundle_adjustment/src/spa2d.cpp:425-609 with useCSparse = SBA_BLOCK_JACOBIAN_PCG).
+// (lesson6/lib/sparse_bundle_adjustment/src/spa2d.cpp:425-609 with useCSparse = SBA_BLOCK_JACOBIAN_PCG), and, as
+// the kernel's second instantiation, with the direct envelope Cholesky solve include/slam2d/spa.h states in
+// place of PCG (the node's doSPA(40) solves directly too, csp.doChol() spa2d.cpp:501-509).
 //
 // One 256-thread workgroup per graph runs the whole LM loop, PCG loops inside, in one launch: no grid-wide
 // synchronisation, no cooperative launch, nothing waits on another workgroup.  A graph's working arrays live in
@@ -10,7 +12,16 @@
 // the comparisons false on every lane alike, so the loops end at their bounds.
 //
 // Arithmetic: IEEE double, -ffp-contract=off, in the orders include/slam2d/spa.h states; tests/ref/spa2d_ref.c
-// restates the same sequence with the reference's scatter loops, and the two agree bit for bit.
+// restates the same sequence with the reference's scatter loops, and the two agree bit for bit; the direct solve
+// is restated row by row in tests/ref/spa2d_chol_ref.c.
+//
+// The direct solve's schedule: the factor goes left-looking by block column j.  Phase A: one lane per row i >= j
+// whose envelope reaches column j forms S = A(i, j) - sum over m < j of L(i, m) L(j, m)' (both rows' blocks are
+// contiguous); lane 0, which owns row j, turns S(j, j) into L(j, j), solves the forward step y(j) -- the forward
+// solve is the factor of the system bordered by b -- and leaves L(j, j) and the pivot flag in LDS.  Phase B: the
+// lanes of the rows below divide by L(j, j)'.  Two barriers per block column.  The backward solve goes by block
+// row m, descending: every lane forms x(m) from y(m) and L(m, m), then one lane per block of row m subtracts
+// L(m, j)' x(m) from y(j); one barrier per row.  Each scalar's subtractions happen in the order spa.h states.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -47,6 +58,9 @@ struct SpaDev {
     const int *pair_off;      // [G][M + 1]: per unordered node pair, its constraints in constraint order
     const int *pair_con;      // [G][M]
     double *scratch;          // [G][spa_scratch_doubles]
+    int max_fac;              // the direct solve's capacity per graph, in 3 x 3 blocks
+    double *fac;              // [G][max_fac][9]: the envelope, row after row; block (i, j) row-major
+    int *fidx;                // [G][spa_fidx_ints]: first [N], last [N], rowoff [N + 1] over the free nodes
     spa_stats *stats;         // [G]
 };
 
@@ -54,6 +68,8 @@ __host__ __device__ inline size_t spa_scratch_doubles(int max_nodes, int max_con
 {
     return (size_t)max_nodes * SPA_NODE_DOUBLES + (size_t)max_cons * SPA_CONS_DOUBLES;
 }
+
+__host__ __device__ inline size_t spa_fidx_ints(int max_nodes) { return (size_t)3 * max_nodes + 1; }
 
 // C = A * B, each element (a0*b0 + a1*b1) + a2*b2
 __device__ inline void spa_mul33(const double *A, const double *B, double *C)
@@ -144,10 +160,208 @@ __device__ inline double spa_cost(int m, const int2 *nd, const double *mean, con
     return spa_reduce(acc, red);
 }
 
+// ---- the direct solve (spa.h "The direct solve"); indices are free-node indices f = k - nF
+
+// first[], last[] and the row offsets of graph's envelope, once per compute.  last[j] is the largest row whose
+// envelope reaches column j (>= j).  Returns the envelope's blocks, read from LDS: the same on every lane.  When
+// they exceed cap, rowoff is not written.
+__device__ inline long long spa_chol_setup(int nF, int nfree, int cap, const int *nbr_off, const int2 *nbr, int *first,
+                                           int *last, int *rowoff, long long *lscan, int *iscan)
+{
+    const int t = threadIdx.x;
+    for (int f = t; f < nfree; f += SPA_THREADS) {
+        const int k = nF + f;
+        int fi = f;
+        for (int j = nbr_off[k]; j < nbr_off[k + 1]; ++j) {
+            const int nb = nbr[j].x;
+            if (nb >= nF) {
+                if (nb < k) fi = nb - nF;
+                break;
+            }
+        }
+        first[f] = fi;
+        last[f] = f;
+    }
+    __syncthreads();
+    for (int f = t; f < nfree; f += SPA_THREADS) atomicMax(&last[first[f]], f);
+    __syncthreads();
+    // prefix sum of the widths and prefix maximum of last[]: lane t scans the segment [lo, hi)
+    const int seg = (nfree + SPA_THREADS - 1) / SPA_THREADS;
+    const int lo = t * seg < nfree ? t * seg : nfree, hi = lo + seg < nfree ? lo + seg : nfree;
+    long long run = 0;
+    int rmax = -1;
+    for (int f = lo; f < hi; ++f) {
+        run += f - first[f] + 1;
+        rmax = last[f] > rmax ? last[f] : rmax;
+    }
+    lscan[t] = run;
+    iscan[t] = rmax;
+    __syncthreads();
+    if (t == 0) {
+        run = 0;
+        rmax = -1;
+        for (int q = 0; q < SPA_THREADS; ++q) {
+            const long long v = lscan[q];
+            const int w = iscan[q];
+            lscan[q] = run;
+            iscan[q] = rmax;
+            run += v;
+            rmax = w > rmax ? w : rmax;
+        }
+        lscan[SPA_THREADS] = run;
+    }
+    __syncthreads();
+    const long long total = lscan[SPA_THREADS];
+    if (total <= cap) {
+        run = lscan[t];
+        rmax = iscan[t];
+        for (int f = lo; f < hi; ++f) {
+            rowoff[f] = (int)run;
+            run += f - first[f] + 1;
+            rmax = last[f] > rmax ? last[f] : rmax;
+            last[f] = rmax;
+        }
+        if (t == 0) rowoff[nfree] = (int)total;
+    }
+    __syncthreads();
+    return total;
+}
+
+// The system into the envelope: zeros, then per free node the lower triangle of its diagonal block and the
+// transposed pair blocks of its lower free neighbours.  Barriers before (diag, pblk) and after.
+__device__ inline void spa_chol_assemble(int nF, int nfree, const int *first, const int *rowoff, const int *nbr_off,
+                                         const int2 *nbr, const double *diag, const double *pblk, double *fac)
+{
+    const int t = threadIdx.x;
+    __syncthreads();
+    const size_t total = (size_t)9 * rowoff[nfree];
+    for (size_t q = t; q < total; q += SPA_THREADS) fac[q] = 0.0;
+    __syncthreads();
+    for (int f = t; f < nfree; f += SPA_THREADS) {
+        const int k = nF + f, fi = first[f];
+        double *Lf = fac + (size_t)9 * rowoff[f];
+        double *Dg = Lf + (size_t)9 * (f - fi);
+        const double *A = diag + 9 * (size_t)k;
+        for (int c = 0; c < 3; ++c)
+            for (int c2 = 0; c2 <= c; ++c2) Dg[3 * c + c2] = A[3 * c2 + c];
+        for (int j = nbr_off[k]; j < nbr_off[k + 1]; ++j) {
+            const int2 nb = nbr[j];
+            if (nb.x < nF) continue;
+            if (nb.x >= k) break;
+            double *Bk = Lf + (size_t)9 * (nb.x - nF - fi);
+            const double *Pb = pblk + 9 * (size_t)nb.y;
+            for (int c = 0; c < 3; ++c)
+                for (int c2 = 0; c2 < 3; ++c2) Bk[3 * c + c2] = Pb[3 * c2 + c];
+        }
+    }
+    __syncthreads();
+}
+
+// Factor in place, forward solve in place in y, backward solve into x.  ljj [6] (l00 l10 l11 l20 l21 l22) and bad
+// are in LDS.  Returns false when a pivot was not > 0: the same on every lane, read from LDS.
+__device__ inline bool spa_chol_solve(int nfree, const int *first, const int *last, const int *rowoff, double *fac,
+                                      double *y, double *x, double *ljj, int *bad)
+{
+    const int t = threadIdx.x;
+    for (int j = 0; j < nfree; ++j) {
+        const int fj = first[j], lastj = last[j];
+        const double *Lj = fac + (size_t)9 * rowoff[j];
+        // phase A
+        for (int i = j + t; i <= lastj; i += SPA_THREADS) {
+            const int fi = first[i];
+            if (fi > j) continue;
+            double *Li = fac + (size_t)9 * rowoff[i];
+            double *S = Li + (size_t)9 * (j - fi);
+            double s[9];
+            for (int q = 0; q < 9; ++q) s[q] = S[q];
+            for (int m = fi > fj ? fi : fj; m < j; ++m) {
+                const double *a = Li + (size_t)9 * (m - fi), *b = Lj + (size_t)9 * (m - fj);
+                for (int c = 0; c < 3; ++c)
+                    for (int c2 = 0; c2 < 3; ++c2)
+                        for (int q = 0; q < 3; ++q) s[3 * c + c2] = s[3 * c + c2] - a[3 * c + q] * b[3 * c2 + q];
+            }
+            if (i == j) {  // lane 0: the pivots, then y(j)
+                int nb = 0;
+                double v = s[0];
+                if (!(v > 0.0)) nb = 1;
+                const double l00 = sqrt(v);
+                const double l10 = s[3] / l00, l20 = s[6] / l00;
+                v = s[4] - l10 * l10;
+                if (!(v > 0.0)) nb = 1;
+                const double l11 = sqrt(v);
+                const double l21 = (s[7] - l20 * l10) / l11;
+                v = s[8] - l20 * l20;
+                v = v - l21 * l21;
+                if (!(v > 0.0)) nb = 1;
+                const double l22 = sqrt(v);
+                double yv[3] = {y[3 * j], y[3 * j + 1], y[3 * j + 2]};
+                for (int m = fj; m < j; ++m) {
+                    const double *b = Lj + (size_t)9 * (m - fj), *ym = y + 3 * (size_t)m;
+                    for (int c = 0; c < 3; ++c)
+                        for (int q = 0; q < 3; ++q) yv[c] = yv[c] - b[3 * c + q] * ym[q];
+                }
+                yv[0] = yv[0] / l00;
+                yv[1] = (yv[1] - l10 * yv[0]) / l11;
+                yv[2] = ((yv[2] - l20 * yv[0]) - l21 * yv[1]) / l22;
+                for (int q = 0; q < 3; ++q) y[3 * j + q] = yv[q];
+                s[0] = l00; s[1] = 0.0; s[2] = 0.0;
+                s[3] = l10; s[4] = l11; s[5] = 0.0;
+                s[6] = l20; s[7] = l21; s[8] = l22;
+                ljj[0] = l00; ljj[1] = l10; ljj[2] = l11; ljj[3] = l20; ljj[4] = l21; ljj[5] = l22;
+                *bad = nb;
+            }
+            for (int q = 0; q < 9; ++q) S[q] = s[q];
+        }
+        __syncthreads();
+        if (*bad) return false;
+        // phase B: L(i, j) = S(i, j) / L(j, j)'
+        const double l00 = ljj[0], l10 = ljj[1], l11 = ljj[2], l20 = ljj[3], l21 = ljj[4], l22 = ljj[5];
+        for (int i = j + 1 + t; i <= lastj; i += SPA_THREADS) {
+            const int fi = first[i];
+            if (fi > j) continue;
+            double *S = fac + (size_t)9 * rowoff[i] + (size_t)9 * (j - fi);
+            for (int c = 0; c < 3; ++c) {
+                const double x0 = S[3 * c] / l00;
+                const double x1 = (S[3 * c + 1] - x0 * l10) / l11;
+                const double x2 = ((S[3 * c + 2] - x0 * l20) - x1 * l21) / l22;
+                S[3 * c] = x0;
+                S[3 * c + 1] = x1;
+                S[3 * c + 2] = x2;
+            }
+        }
+        __syncthreads();
+    }
+    for (int m = nfree - 1; m >= 0; --m) {
+        const int fm = first[m];
+        const double *Lm = fac + (size_t)9 * rowoff[m];
+        const double *Dg = Lm + (size_t)9 * (m - fm);
+        const double x2 = y[3 * m + 2] / Dg[8];
+        const double x1 = (y[3 * m + 1] - Dg[7] * x2) / Dg[4];
+        const double x0 = ((y[3 * m] - Dg[6] * x2) - Dg[3] * x1) / Dg[0];
+        if (t == 0) {
+            x[3 * m] = x0;
+            x[3 * m + 1] = x1;
+            x[3 * m + 2] = x2;
+        }
+        for (int j = fm + t; j < m; j += SPA_THREADS) {
+            const double *b = Lm + (size_t)9 * (j - fm);
+            double *yj = y + 3 * (size_t)j;
+            for (int c = 0; c < 3; ++c) yj[c] = ((yj[c] - b[6 + c] * x2) - b[3 + c] * x1) - b[c] * x0;
+        }
+        __syncthreads();
+    }
+    return true;
+}
+
+template <int SOLVER>
 __global__ __launch_bounds__(SPA_THREADS) void spa_solve_kernel(SpaDev D, int g_first, spa_params P)
 {
     __shared__ double red[SPA_THREADS];
     __shared__ int bc[5];
+    constexpr bool CHOL = SOLVER == SPA_SOLVER_CHOLESKY;
+    __shared__ long long lscan[CHOL ? SPA_THREADS + 1 : 1];
+    __shared__ int iscan[CHOL ? SPA_THREADS : 1];
+    __shared__ double ljj[CHOL ? 6 : 1];
     const int t = threadIdx.x;
     const int g = g_first + blockIdx.x;
     const size_t N = (size_t)D.max_nodes, M = (size_t)D.max_cons;
@@ -212,6 +426,17 @@ __global__ __launch_bounds__(SPA_THREADS) void spa_solve_kernel(SpaDev D, int g_
         __syncthreads();
         if (bc[3]) {
             st.status = SPA_DISCONNECTED;
+            if (t == 0) D.stats[g] = st;
+            return;
+        }
+    }
+
+    // the direct solve's envelope; one that does not fit the context's factor storage is refused
+    int *first = D.fidx + g * spa_fidx_ints(D.max_nodes), *last = first + N, *rowoff = last + N;
+    double *fac = D.fac + g * (size_t)D.max_fac * 9;
+    if constexpr (CHOL) {
+        if (spa_chol_setup(nF, nfree, D.max_fac, nbr_off, nbr, first, last, rowoff, lscan, iscan) > D.max_fac) {
+            st.status = SPA_FACTOR_RANGE;
             if (t == 0) D.stats[g] = st;
             return;
         }
@@ -284,6 +509,11 @@ __global__ __launch_bounds__(SPA_THREADS) void spa_solve_kernel(SpaDev D, int g_
                 for (int q = 0; q < 3; ++q) b[q] -= o[27 + 3 * end + q];
             }
             A[0] *= lam; A[4] *= lam; A[8] *= lam;
+            if constexpr (CHOL) {  // the direct solve reads the block and B only
+                for (int q = 0; q < 9; ++q) diag[9 * k + q] = A[q];
+                for (int q = 0; q < 3; ++q) vB[3 * k + q] = b[q];
+                continue;
+            }
             double Ji[9], dd[3];
             spa_inv33(A, Ji);
             spa_mv3(Ji, b, dd);  // r = b; mD(J, r, d)
@@ -315,6 +545,19 @@ __global__ __launch_bounds__(SPA_THREADS) void spa_solve_kernel(SpaDev D, int g_
             }
             for (int q = 0; q < 9; ++q) pblk[9 * (size_t)p + q] = Bk[q];
         }
+        if constexpr (CHOL) {
+            // ---- the direct solve in place of doChol (spa2d.cpp:501-509): B -> y in place, the step into x; the
+            // pivot flag lives in bc[3], free since the disconnected check
+            if (nfree > 0) {
+                spa_chol_assemble(nF, nfree, first, rowoff, nbr_off, nbr, diag, pblk, fac);
+                if (!spa_chol_solve(nfree, first, last, rowoff, fac, vB + 3 * (size_t)nF, vx + 3 * (size_t)nF, ljj, &bc[3])) {
+                    st.status = SPA_NOT_POSDEF;
+                    break;
+                }
+            } else {
+                __syncthreads();
+            }
+        } else
         // ---- doBPCG (csparse.cpp:737-749) -> doBPCG2 (bpcg.h:284-315); skipped when B has no rows (:485)
         if (nfree > 0) {
             double dn = spa_reduce(acc, red);  // r.dot(d); its barriers also publish d and the pair blocks

@@ -2,10 +2,11 @@
 
 Reference: MapperGraph::CorrectPoses (lesson6/lib/open_karto/src/Mapper.cpp:1397-1414) -> SpaSolver::Compute
 (lesson6/src/spa_solver/spa_solver.cc:43-61) -> SysSPA2d::doSPA (lesson6/lib/sparse_bundle_adjustment/src/
-spa2d.cpp:425-609), run here in its block-Jacobi PCG mode (SBA_BLOCK_JACOBIAN_PCG), not the node's sparse-Cholesky
-default.  `SpaSolver` carries the reference's method names; `SpaFleet` holds a batch of independent graphs.  Results
-are checked against tests/ref/spa2d_ref.c (parity unpinned against the compiled library: Eigen and SuiteSparse are
-absent).
+spa2d.cpp:425-609), run here in its block-Jacobi PCG mode (SBA_BLOCK_JACOBIAN_PCG, solver="pcg", the default) or with
+a direct envelope Cholesky solve (solver="cholesky"; the node's doSPA(40) solves directly too, through CSparse /
+CHOLMOD in an order of their own).  `SpaSolver` carries the reference's method names; `SpaFleet` holds a batch of
+independent graphs.  Results are checked against tests/ref/spa2d_ref.c and tests/ref/spa2d_chol_ref.c (parity
+unpinned against the compiled library: Eigen and SuiteSparse are absent).
 """
 from __future__ import annotations
 
@@ -18,12 +19,14 @@ from . import _lib
 from ._lib import Slam2dError
 
 SPA_OK, SPA_EINVAL, SPA_ERANGE = 0, -1, -5
-SPA_NOT_RUN, SPA_NO_FIXED, SPA_DISCONNECTED = -100, 1, 2
+SPA_NOT_RUN, SPA_NO_FIXED, SPA_DISCONNECTED, SPA_NOT_POSDEF, SPA_FACTOR_RANGE = -100, 1, 2, 3, 4
+SPA_SOLVER_PCG, SPA_SOLVER_CHOLESKY = 0, 1
+SOLVERS = {"pcg": SPA_SOLVER_PCG, "cholesky": SPA_SOLVER_CHOLESKY}
 SPA_FIXED_FROM_PARAMS = -2147483648
 
 
 class SpaParams(C.Structure):
-    _fields_ = [("niter", C.c_int), ("max_cg_iters", C.c_int), ("n_fixed", C.c_int), ("pad_", C.c_int),
+    _fields_ = [("niter", C.c_int), ("max_cg_iters", C.c_int), ("n_fixed", C.c_int), ("solver", C.c_int),
                 ("lambda_", C.c_double), ("init_tol", C.c_double)]
 
 
@@ -47,6 +50,8 @@ def _declare(L):
     L.spa_default_params.restype = None
     L.spa_default_params.argtypes = [P(SpaParams)]
     L.spa_create.argtypes = [P(vp), i, i, i]
+    L.spa_create_ex.argtypes = [P(vp), i, i, i, i]
+    L.spa_envelope_blocks.argtypes = [vp, i, i, P(C.c_longlong)]
     L.spa_destroy.argtypes = [vp]
     L.spa_add_node.argtypes = [vp, i, i, vp]
     L.spa_add_constraint.argtypes = [vp, i, i, i, vp, vp, P(i)]
@@ -64,16 +69,20 @@ def _declare(L):
 
 
 def default_params(**kw) -> SpaParams:
-    """spa_default_params: niter 40, max_cg_iters 50, n_fixed 1, lambda 1e-4, init_tol 1e-8; keywords override
-    (`lambda_` or `lambda` for the augmentation)."""
+    """spa_default_params: niter 40, max_cg_iters 50, n_fixed 1, lambda 1e-4, init_tol 1e-8, solver "pcg"; keywords
+    override (`lambda_` or `lambda` for the augmentation; solver="pcg" | "cholesky" or the SPA_SOLVER_* value)."""
     L = _lib.lib()
     _declare(L)
     p = SpaParams()
     L.spa_default_params(C.byref(p))
     for k, v in kw.items():
         k = "lambda_" if k == "lambda" else k
-        if k not in ("niter", "max_cg_iters", "n_fixed", "lambda_", "init_tol"):
+        if k not in ("niter", "max_cg_iters", "n_fixed", "lambda_", "init_tol", "solver"):
             raise TypeError(f"unknown parameter {k}")
+        if k == "solver":
+            if v not in SOLVERS and v not in SOLVERS.values():
+                raise ValueError(f"solver must be one of {sorted(SOLVERS)}")
+            v = SOLVERS.get(v, v)
         setattr(p, k, v)
     return p
 
@@ -171,15 +180,18 @@ def _hp(a):
 
 
 class SpaFleet:
-    """A batch of `max_graphs` independent pose graphs, device resident; one workgroup optimises each."""
+    """A batch of `max_graphs` independent pose graphs, device resident; one workgroup optimises each.
+    `max_factor_blocks` is the direct solve's room per graph in 3 x 3 blocks (see envelope_blocks); 0 serves the PCG
+    mode only."""
 
-    def __init__(self, max_graphs: int, max_nodes: int, max_constraints: int):
+    def __init__(self, max_graphs: int, max_nodes: int, max_constraints: int, max_factor_blocks: int = 0):
         self.L = _lib.lib()
         _declare(self.L)
         self.max_graphs, self.max_nodes, self.max_constraints = int(max_graphs), int(max_nodes), int(max_constraints)
+        self.max_factor_blocks = int(max_factor_blocks)
         self.h = C.c_void_p()
-        self._check(self.L.spa_create(C.byref(self.h), self.max_graphs, self.max_nodes, self.max_constraints),
-                    "spa_create")
+        self._check(self.L.spa_create_ex(C.byref(self.h), self.max_graphs, self.max_nodes, self.max_constraints,
+                                         self.max_factor_blocks), "spa_create_ex")
 
     def _check(self, rc, what):
         if rc != 0:
@@ -233,6 +245,12 @@ class SpaFleet:
         self._check(self.L.spa_get_counts(self.h, g, C.byref(n), C.byref(m)), "spa_get_counts")
         return n.value, m.value
 
+    def envelope_blocks(self, g: int, n_fixed: int = 1) -> int:
+        """spa_envelope_blocks: the 3 x 3 blocks graph g's factor needs with its first n_fixed nodes fixed."""
+        blocks = C.c_longlong(0)
+        self._check(self.L.spa_envelope_blocks(self.h, g, int(n_fixed), C.byref(blocks)), "spa_envelope_blocks")
+        return blocks.value
+
     def compute(self, g_first: int = 0, count: int | None = None, params: SpaParams | None = None):
         """doSPA on graphs [g_first, g_first + count), waiting for the result."""
         count = self.max_graphs - g_first if count is None else count
@@ -271,11 +289,18 @@ class SpaFleet:
 
 class SpaSolver:
     """lesson6's SpaSolver (spa_solver.cc:32-91) over one device graph: AddNode, AddConstraint, Compute,
-    GetCorrections, Clear."""
+    GetCorrections, Clear.  solver="cholesky" selects the direct solve, with factor storage for the full triangle of
+    max_nodes; `params`, when given, is used as it is and its solver field must agree."""
 
-    def __init__(self, max_nodes: int = 2048, max_constraints: int = 8192, params: SpaParams | None = None):
-        self.fleet = SpaFleet(1, max_nodes, max_constraints)
-        self.params = params if params is not None else default_params()
+    def __init__(self, max_nodes: int = 2048, max_constraints: int = 8192, params: SpaParams | None = None,
+                 solver: str = "pcg"):
+        if solver not in SOLVERS:
+            raise ValueError(f"solver must be one of {sorted(SOLVERS)}")
+        self.params = params if params is not None else default_params(solver=solver)
+        if self.params.solver != SOLVERS[solver]:
+            raise ValueError("params.solver and solver disagree")
+        blocks = max_nodes * (max_nodes + 1) // 2 if solver == "cholesky" else 0
+        self.fleet = SpaFleet(1, max_nodes, max_constraints, blocks)
         self.corrections: list = []
 
     def close(self):

@@ -1,5 +1,5 @@
-/* include/slam2d/spa.h -- C-ABI of the MI355X Karto pose-graph optimiser (lesson6, config 5): SPA in its
- * block-Jacobi PCG mode, for a fleet of independent graphs.
+/* include/slam2d/spa.h -- C-ABI of the MI355X Karto pose-graph optimiser (lesson6, config 5): SPA with its
+ * block-Jacobi PCG solve or a direct envelope Cholesky solve, for a fleet of independent graphs.
  *
  * Reference: MapperGraph::CorrectPoses (lesson6/lib/open_karto/src/Mapper.cpp:1397-1414) calls
  * SpaSolver::Compute (lesson6/src/spa_solver/spa_solver.cc:43-61), which calls SysSPA2d::doSPA
@@ -9,9 +9,12 @@
  *
  * the mode whose arithmetic is all in the reference's own text (setupSparseSys spa2d.cpp:328-413,
  * CSparse2d::incDiagBlocks / doBPCG csparse.cpp:488-492, :737-749, jacobiBPCG<3>::doBPCG2 / mMV2
- * bpcg/bpcg.h:142-161, :237-316).  The node itself calls doSPA(40), whose default linear solver is sparse
- * Cholesky through CSparse / CHOLMOD, libraries outside the reference tree: that mode is NOT built.  Both
- * modes minimise the same cost; their iterates differ.
+ * bpcg/bpcg.h:142-161, :237-316), when spa_params.solver is SPA_SOLVER_PCG (the default).  The node itself calls
+ * doSPA(40), whose default linear solver is the direct sparse Cholesky solve csp.doChol() (spa2d.cpp:501-509)
+ * through CSparse's cs_cholsol / CHOLMOD, libraries outside the reference tree.  SPA_SOLVER_CHOLESKY selects a
+ * direct solve as well, in an evaluation order of this library's own, stated below ("The direct solve"); an
+ * ordering changes only the rounding of a Cholesky solve, not its solution.  Everything in doSPA outside the
+ * linear solve is the same in both modes.  Both minimise the same cost; their iterates differ.
  *
  *   spa_add_node        SysSPA2d::addNode (spa2d.cpp:207-222)
  *   spa_add_constraint  SysSPA2d::addConstraint (spa2d.cpp:230-252)
@@ -28,6 +31,31 @@
  *   - every vector reduction (r.d, d.q, r.s, the step's squared norm, the cost) has ONE shape, SPA_REDUCE_LANES
  *     = 256 lanes: lane t adds the terms of free node (or constraint) t, t + 256, ... in ascending order onto
  *     +0.0, a node's term being its 3-term dot; then s[t] += s[t + 128], s[t] += s[t + 64], ..., s[0] += s[1].
+ *
+ * The direct solve (SPA_SOLVER_CHOLESKY).  tests/ref/spa2d_chol_ref.c restates it row by row; the kernel's
+ * parallel schedule gives the same bits.  nF is the number of fixed nodes, node indices below are free-node
+ * indices k - nF, and free node k owns the scalar rows 3k + c, c = 0, 1, 2.
+ *   System.  Only the upper triangle of the block system enters, as in setupCSstructure (csparse.cpp:553-631).
+ *     The working matrix A is lower triangular: for c' <= c, A(3k + c, 3k + c') = diag_k[c'][c], diag_k being the
+ *     node's diagonal block after incDiagBlocks (its three diagonal elements times 1 + lambda, csparse.cpp:629);
+ *     for a pair of free nodes j < k with a constraint, A(3k + c, 3j + c') = pblk_(j,k)[c'][c], pblk_(j,k) being
+ *     the block addOffdiagBlock keeps at (row j, column k).
+ *   Envelope, natural order (the order cs_cholsol itself uses up to csize = 100, csparse.cpp:722-726).  first[k]
+ *     is the smallest free neighbour of k when that is < k, else k.  Scalar row 3k + c spans the columns
+ *     start = 3 first[k] ... 3k + c; structural zeros inside the span are ordinary +0.0 entries.  A graph's
+ *     envelope has sum over free k of (k - first[k] + 1) blocks of 3 x 3 (spa_envelope_blocks).
+ *   Factor A = L L'.  For row i and column j <= i inside the envelope: v = A(i, j); for m ascending from
+ *     max(start_i, start_j) to j - 1, v = v - L(i, m) * L(j, m), one subtraction at a time; then L(i, j) =
+ *     v / L(j, j) for j < i and L(i, i) = sqrt(v) (IEEE, correctly rounded).  Any schedule that yields these
+ *     bits is allowed.
+ *   Solve.  Forward: y(i) = (b(i) - sum L(i, m) * y(m)) / L(i, i), m ascending from start_i, subtracted one at a
+ *     time.  Backward: x(i) = (y(i) - sum L(m, i) * x(m)) / L(i, i) over the rows m > i with start_m <= i, in
+ *     descending m, subtracted one at a time.  x is the step BB holds at spa2d.cpp:519.
+ *   Failure.  A pivot with !(v > 0) -- zero, negative or NaN -- ends that graph's compute with the status
+ *     SPA_NOT_POSDEF: the poses are as the last completed LM iteration left them, the stats those to date
+ *     (lm_iters counts the iteration whose factor failed).  The reference prints "Sparse Cholesky failed!" and
+ *     steps by the untouched right-hand side; this library refuses instead.
+ *   cg_iters stays 0 in this mode.
  *
  * Conventions as in karto_grid.h: plain C types, int status (SPA_OK / negative), spa_last_error().  A pose
  * is double[3] = x, y, heading (rad); a precision matrix is double[9], row-major.
@@ -54,6 +82,14 @@ extern "C" {
 #define SPA_NO_FIXED 1       /* n_fixed <= 0 (spa2d.cpp:435-439): 0 iterations, poses untouched */
 #define SPA_DISCONNECTED 2   /* a free node has no constraint: refused, poses untouched (the reference prints
                                 "disconnected nodes" and inverts a zero block) */
+#define SPA_NOT_POSDEF 3     /* SPA_SOLVER_CHOLESKY: a pivot was not > 0 (zero, negative or NaN).  Poses as the last
+                                completed LM iteration left them, stats to date (the reference prints "Sparse
+                                Cholesky failed!" and steps by the right-hand side) */
+#define SPA_FACTOR_RANGE 4   /* SPA_SOLVER_CHOLESKY: the graph's envelope has more blocks than the context's
+                                max_factor_blocks: refused, poses untouched */
+
+#define SPA_SOLVER_PCG 0      /* block-Jacobi preconditioned conjugate gradients (SBA_BLOCK_JACOBIAN_PCG) */
+#define SPA_SOLVER_CHOLESKY 1 /* direct envelope Cholesky in natural order ("The direct solve" above) */
 
 #define SPA_REDUCE_LANES 256
 #define SPA_FIXED_FROM_PARAMS (-2147483647 - 1)
@@ -65,17 +101,17 @@ typedef struct spa_params {
     int niter;        /* LM iterations at most: 40 (spa_solver.cc:51) */
     int max_cg_iters; /* PCG iterations per LM iteration at most: 50 (spa2d.h:249) */
     int n_fixed;      /* the first n_fixed nodes stay put: 1 (spa2d.h:198) */
-    int pad_;
+    int solver;       /* SPA_SOLVER_PCG (0, the default) or SPA_SOLVER_CHOLESKY; anything else is SPA_EINVAL */
     double lambda;    /* LM diagonal augmentation, re-initialised by every compute: 1e-4; must be > 0 */
     double init_tol;  /* PCG relative tolerance: 1e-8 */
 } spa_params;
 
 typedef struct spa_stats {
-    int status;      /* SPA_OK, SPA_NO_FIXED, SPA_DISCONNECTED or SPA_NOT_RUN */
+    int status;      /* SPA_OK, SPA_NO_FIXED, SPA_DISCONNECTED, SPA_NOT_POSDEF, SPA_FACTOR_RANGE or SPA_NOT_RUN */
     int good_iter;   /* doSPA's return value: accepted steps */
     int lm_iters;    /* LM iterations begun (linear systems set up), the converging one included */
     int rejected;    /* steps undone because the cost did not fall */
-    int cg_iters;    /* PCG iterations, all LM iterations together */
+    int cg_iters;    /* PCG iterations, all LM iterations together; 0 with SPA_SOLVER_CHOLESKY */
     int converged;   /* 1: ended by sqDiff < sqMinDelta (spa2d.cpp:523-529); 0: by niter */
     double initial_cost, final_cost; /* calcCost (spa2d.cpp:173-201) before the first and after the last step */
     double lambda;   /* the final lambda */
@@ -90,6 +126,11 @@ void spa_default_params(spa_params *params);
 /* A fleet of max_graphs graphs of up to max_nodes nodes and max_constraints constraints each, all device
  * resident.  Every graph starts empty. */
 int spa_create(spa_ctx **out, int max_graphs, int max_nodes, int max_constraints);
+/* The same with room for the direct solve's factor: max_factor_blocks 3 x 3 blocks per graph (0 .. 2^27), the
+ * sum over a graph's free nodes of k - first[k] + 1.  spa_create means 0: every SPA_SOLVER_CHOLESKY compute of a
+ * graph with a free node then ends with SPA_FACTOR_RANGE.  The factor costs about the sum of the squared row
+ * widths (k - first[k] + 1) in 3 x 3 products per LM iteration. */
+int spa_create_ex(spa_ctx **out, int max_graphs, int max_nodes, int max_constraints, int max_factor_blocks);
 int spa_destroy(spa_ctx *ctx);
 
 /* addNode: appends a node; its index is the count before.  Ids need not be unique. */
@@ -107,6 +148,10 @@ int spa_clear_graph(spa_ctx *ctx, int g);
  * later compute.  SPA_FIXED_FROM_PARAMS (the initial state) goes back to params->n_fixed. */
 int spa_set_n_fixed(spa_ctx *ctx, int g, int n_fixed);
 int spa_get_counts(spa_ctx *ctx, int g, int *n_nodes, int *n_cons);
+/* The blocks of graph g's envelope when its first n_fixed nodes are fixed (n_fixed as a compute would use it: the
+ * graph's own value or params->n_fixed; <= 0 gives 0 blocks): counted on the host from the neighbour lists, to size
+ * a context or to predict SPA_FACTOR_RANGE. */
+int spa_envelope_blocks(spa_ctx *ctx, int g, int n_fixed, long long *blocks);
 
 /* doSPA on graphs [g_first, g_first + count).  Poses persist: a later compute starts from the optimised
  * poses, as m_Spa does.  No solver state crosses calls (lambda is re-initialised, spa2d.cpp:452-453; abstol

@@ -2,13 +2,19 @@
 """Times the pose-graph optimiser (spa_compute_device, one workgroup per graph) on fleets of ring-with-closure graphs
 and the CPU restatement (tests/ref/spa2d_ref.c, one core) on one such graph beside it.
 
-    python tools/bench_spa.py [--nodes 64 512 2048] [--graphs 256] [--reps 5] [--out profiles/spa_bench.json]
+    python tools/bench_spa.py [--nodes 64 512 2048] [--graphs 256] [--reps 5] [--solver pcg|cholesky]
+                              [--out profiles/spa_bench.json]
 
 Every repetition reloads the same drifted graphs (spa_set_graph, not timed) and times one spa_compute_device between
 two events on the context's stream, so each timed compute does the same work: the reference's default parameters
 (40 LM iterations, lambda 1e-4, tolerance 1e-8, 50 PCG iterations).  Reported per size: ms per compute (median and
 minimum over the repetitions), graphs per second, the LM and PCG iterations of graph 0 and the restatement's seconds
 for one graph (the fastest of three runs).  The first, untimed compute checks graph 0 against the restatement bit for bit.
+
+--solver cholesky times the direct mode beside the PCG mode on the same graphs and contexts, the two alternating
+repetition by repetition so that both see the same machine, and writes its rows under "cholesky_rows" (ms per compute,
+graphs per second, LM iterations, the envelope's blocks and the cost model sum of squared row widths); its first
+compute is checked against tests/ref/spa2d_chol_ref.c.
 """
 import argparse
 import json
@@ -26,6 +32,8 @@ def main() -> int:
     ap.add_argument("--nodes", type=int, nargs="+", default=[64, 512, 2048])
     ap.add_argument("--graphs", type=int, default=256, help="graphs per fleet (one workgroup each)")
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--solver", choices=["pcg", "cholesky"], default="pcg",
+                    help="cholesky: the direct mode's rows beside the PCG rows")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "spa_bench.json"))
     a = ap.parse_args()
 
@@ -36,7 +44,9 @@ def main() -> int:
 
     assert torch.cuda.is_available(), "bench_spa needs a HIP device"
     prm = spa.default_params()
-    rows = []
+    solvers = ["pcg", "cholesky"] if a.solver == "cholesky" else ["pcg"]
+    prms = {"pcg": prm, "cholesky": spa.default_params(solver="cholesky")}
+    rows, chol_rows = [], []
     for n in a.nodes:
         cases = [R.case_ring(n, 1000 + g) for g in range(min(a.graphs, 8))]  # eight distinct graphs, repeated
         m = len(cases[0]["ends"])
@@ -46,8 +56,18 @@ def main() -> int:
             t0 = time.perf_counter()
             want_poses, want_stats = R.compute_case(cases[0])
             ref_s = min(ref_s, time.perf_counter() - t0)
+        blocks = 0
+        if a.solver == "cholesky":
+            import numpy as np
+
+            import spa2d_chol_ref as CH
+
+            blocks = max(CH.envelope_blocks(c) for c in cases)
+            first = CH.first_of(n, cases[0]["ends"], 1)
+            sum_width2 = int(np.sum((np.arange(len(first)) - first + 1).astype(np.int64) ** 2))
+            chol_want = CH.compute_case(cases[0])
         for G in sorted({1, a.graphs}):
-            f = spa.SpaFleet(G, n, m)
+            f = spa.SpaFleet(G, n, m, blocks)
 
             def load():
                 for g in range(G):
@@ -58,19 +78,36 @@ def main() -> int:
             f.compute(0, G, prm)  # warm-up, and the parity check
             R.assert_same_result(f.get_nodes(0)[1], f.stats(0), want_poses, want_stats, f"n={n} G={G}")
             st = f.stats(0)
-            ms = []
+            sts = {"pcg": st}
+            if a.solver == "cholesky":
+                load()
+                f.compute(0, G, prms["cholesky"])  # warm-up of the second instantiation, and its parity check
+                R.assert_same_result(f.get_nodes(0)[1], f.stats(0), *chol_want, f"cholesky n={n} G={G}")
+                sts["cholesky"] = f.stats(0)
+            times = {k: [] for k in solvers}
             stream = torch.cuda.Stream()
             for _ in range(a.reps):
-                load()
-                for g in range(G):
-                    f.device_poses(g)  # uploads the edited graph: not timed
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                f.compute_device(0, G, prm, hip_stream=stream.cuda_stream)
-                e1.record(stream)
-                e1.synchronize()
-                ms.append(e0.elapsed_time(e1))
+                for k in solvers:  # alternating: both solvers see the same machine
+                    load()
+                    for g in range(G):
+                        f.device_poses(g)  # uploads the edited graph: not timed
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(stream)
+                    f.compute_device(0, G, prms[k], hip_stream=stream.cuda_stream)
+                    e1.record(stream)
+                    e1.synchronize()
+                    times[k].append(e0.elapsed_time(e1))
             f.close()
+            if a.solver == "cholesky":
+                ms, st = times["cholesky"], sts["cholesky"]
+                med = statistics.median(ms)
+                chol_rows.append({"nodes": n, "constraints": m, "graphs": G, "ms_per_compute_median": med,
+                                  "ms_per_compute_min": min(ms), "ms_per_compute_max": max(ms),
+                                  "graphs_per_s": G / (med * 1e-3), "lm_iters": st["lm_iters"],
+                                  "good_iter": st["good_iter"], "converged": st["converged"],
+                                  "envelope_blocks": blocks, "sum_width_squared": sum_width2, "reps": a.reps})
+                print(json.dumps({"solver": "cholesky", **chol_rows[-1]}))
+            ms, st = times["pcg"], sts["pcg"]
             med = statistics.median(ms)
             rows.append({"nodes": n, "constraints": m, "graphs": G, "ms_per_compute_median": med,
                          "ms_per_compute_min": min(ms), "graphs_per_s": G / (med * 1e-3), "lm_iters": st["lm_iters"],
@@ -81,6 +118,11 @@ def main() -> int:
                                                                  "lambda": prm.lambda_, "init_tol": prm.init_tol},
            "method": "one spa_compute_device between two events on one stream; graphs reloaded before each repetition",
            "rows": rows}
+    if a.solver == "cholesky":
+        out["cholesky_rows"] = chol_rows
+        out["cholesky_method"] = ("the same graphs and contexts; PCG and Cholesky computes alternate repetition by "
+                                  "repetition; sum_width_squared is the factor's cost model in 3 x 3 products per LM "
+                                  "iteration")
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(out, fh, indent=1)
