@@ -793,10 +793,10 @@ __device__ __forceinline__ void gn_step_cw(const float *__restrict__ cells, cons
     unsigned short *wl0 = reinterpret_cast<unsigned short *>(seqT);  // the miss lists
     __builtin_amdgcn_s_setprio(PRECHAIN_PRIO);
     if (wave != cw) {
-        // the moved points' neighbourhoods go straight from HBM into the cache planes by LDS-DMA (no VGPRs hold
-        // them; the transform is recomputed for the terms below)
+        // the moved points' neighbourhoods go from HBM into the cache planes: by LDS-DMA on a level's first step (no
+        // VGPRs hold them), through a packed pass's registers on the others; the transform is recomputed for the
+        // terms below
         unsigned key[NP];
-        bool miss[NP];
         // every slot's key first, then the gathers of the moved points (the cached keys are registers: a slot
         // is only ever looked up by the thread that owns it)
         const unsigned (&kv)[NP] = kreg;
@@ -811,59 +811,90 @@ __device__ __forceinline__ void gn_step_cw(const float *__restrict__ cells, cons
             const bool in = (slot < n) & (x >= 0.0f) & (x <= lim0) & (y >= 0.0f) & (y <= lim1);  // NaN -> out of map
             key[j] = in ? ((unsigned)(int)y << 16) | (unsigned)(int)x : NB_NONE;  // a slot >= n: no miss
         }
-        const int pw = pt >> 6;
+        const int pw = __builtin_amdgcn_readfirstlane(pt >> 6);  // (uniform: the point wave's rank)
         float *nbf = reinterpret_cast<float *>(nb_val);  // four planes of CW_MAXN floats (cell 00, 10, 01, 11)
+        if (first) {
+            // a level's first step: every in-map point misses (the keys were reset), so each slot's gather is
+            // dense.  Each point thread converts its own slots chunk by chunk below, so chunk 0's terms -- and the
+            // chain -- start after one sixth of the conversions, and chunk j + 1's overlap the chain's chunk j
+            // (no miss list: the conversions need none)
 #pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            miss[j] = key[j] != NB_NONE && kv[j] != key[j];
-            if (miss[j]) {
-                // LDS-DMA: lane l of this wave lands at plane + (pw * 64 + j * CW_PTS) + l = its slot
-                const int sb = pw * 64 + j * CW_PTS;
-                const unsigned ux = key[j] & 0xFFFFu, uy = key[j] >> 16;
-                const float *a0, *a1, *a2, *a3;
-                if (BIG) {  // (levels of 2^30 words or more: 64-bit addresses)
-                    a0 = cells + cell_word(g, (int)ux, (int)uy);
-                    a1 = cells + cell_word(g, (int)ux + 1, (int)uy);
-                    a2 = cells + cell_word(g, (int)ux, (int)uy + 1);
-                    a3 = cells + cell_word(g, (int)ux + 1, (int)uy + 1);
-                } else {
-                    const char *cb = reinterpret_cast<const char *>(cells);
-                    a0 = reinterpret_cast<const float *>(cb + 4u * cell_off(g, ux, uy));
-                    a1 = reinterpret_cast<const float *>(cb + 4u * cell_off(g, ux + 1u, uy));
-                    a2 = reinterpret_cast<const float *>(cb + 4u * cell_off(g, ux, uy + 1u));
-                    a3 = reinterpret_cast<const float *>(cb + 4u * cell_off(g, ux + 1u, uy + 1u));
+            for (int j = 0; j < NP; ++j) {
+                if (key[j] != NB_NONE) {
+                    // LDS-DMA: lane l of this wave lands at plane + (pw * 64 + j * CW_PTS) + l = its slot
+                    const int sb = pw * 64 + j * CW_PTS;
+                    const unsigned ux = key[j] & 0xFFFFu, uy = key[j] >> 16;
+                    const float *a0, *a1, *a2, *a3;
+                    if (BIG) {  // (levels of 2^30 words or more: 64-bit addresses)
+                        a0 = cells + cell_word(g, (int)ux, (int)uy);
+                        a1 = cells + cell_word(g, (int)ux + 1, (int)uy);
+                        a2 = cells + cell_word(g, (int)ux, (int)uy + 1);
+                        a3 = cells + cell_word(g, (int)ux + 1, (int)uy + 1);
+                    } else {
+                        const char *cb = reinterpret_cast<const char *>(cells);
+                        a0 = reinterpret_cast<const float *>(cb + 4u * cell_off(g, ux, uy));
+                        a1 = reinterpret_cast<const float *>(cb + 4u * cell_off(g, ux + 1u, uy));
+                        a2 = reinterpret_cast<const float *>(cb + 4u * cell_off(g, ux, uy + 1u));
+                        a3 = reinterpret_cast<const float *>(cb + 4u * cell_off(g, ux + 1u, uy + 1u));
+                    }
+                    typedef __attribute__((address_space(1))) void gv;
+                    typedef __attribute__((address_space(3))) void lv;
+                    __builtin_amdgcn_global_load_lds((gv *)a0, (lv *)(nbf + 0 * CW_MAXN + sb), 4, 0, 0);
+                    __builtin_amdgcn_global_load_lds((gv *)a1, (lv *)(nbf + 1 * CW_MAXN + sb), 4, 0, 0);
+                    __builtin_amdgcn_global_load_lds((gv *)a2, (lv *)(nbf + 2 * CW_MAXN + sb), 4, 0, 0);
+                    __builtin_amdgcn_global_load_lds((gv *)a3, (lv *)(nbf + 3 * CW_MAXN + sb), 4, 0, 0);
+                    kreg[j] = key[j];
                 }
-                typedef __attribute__((address_space(1))) void gv;
-                typedef __attribute__((address_space(3))) void lv;
-                __builtin_amdgcn_global_load_lds((gv *)a0, (lv *)(nbf + 0 * CW_MAXN + sb), 4, 0, 0);
-                __builtin_amdgcn_global_load_lds((gv *)a1, (lv *)(nbf + 1 * CW_MAXN + sb), 4, 0, 0);
-                __builtin_amdgcn_global_load_lds((gv *)a2, (lv *)(nbf + 2 * CW_MAXN + sb), 4, 0, 0);
-                __builtin_amdgcn_global_load_lds((gv *)a3, (lv *)(nbf + 3 * CW_MAXN + sb), 4, 0, 0);
             }
-        }
-        // list the slot of every miss for this wave (the list lives in the term buffer: chunk 0 is stored after
-        // a barrier that follows every wave's conversions)
-        unsigned short *wl = reinterpret_cast<unsigned short *>(seqT) + pw * (NP * 64);
-        int nmiss = 0;
+            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this wave's LDS-DMA landed (the barrier below publishes it)
+        } else {
+            // the other steps: a few points per hundred change their cell, yet nearly every slot of 64 has one that
+            // did, so a gather per slot would run six lane-sparse blocks.  Instead the wave lists its misses (the
+            // list lives in the term buffer: chunk 0 is stored after a barrier that follows every wave's
+            // conversions), parks each one's key in the slot's own plane-0 word (stale, about to be overwritten),
+            // and gathers them packed: lane e takes list entry e, normally in one pass
+            unsigned short *wl = reinterpret_cast<unsigned short *>(seqT) + pw * (NP * 64);
+            unsigned *nbu = reinterpret_cast<unsigned *>(nb_val);
+            int nmiss = 0;
 #pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            const int slot = pt + j * CW_PTS;
-            const unsigned long long bm = __ballot(miss[j]);
-            if (miss[j]) {
-                kreg[j] = key[j];
-                // (a first step keeps no list: its terms may already fill the buffer the lists live in)
-                if (!first)
+            for (int j = 0; j < NP; ++j) {
+                const int slot = pt + j * CW_PTS;
+                const bool miss = key[j] != NB_NONE && kv[j] != key[j];
+                const unsigned long long bm = __ballot(miss);
+                if (miss) {
+                    kreg[j] = key[j];
                     wl[nmiss + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0u))] =
                         (unsigned short)slot;
+                    nbu[slot] = key[j];
+                }
+                nmiss += __popcll(bm);
             }
-            nmiss += __popcll(bm);
-        }
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this wave's LDS-DMA landed (the barrier below publishes it)
-        if (first) {
-            // a level's first step: every in-map point missed (the keys were reset); each point thread converts its
-            // own slots chunk by chunk below, so chunk 0's terms -- and the chain -- start after one sixth of the
-            // conversions, and chunk j + 1's overlap the chain's chunk j
-        } else {
+            // the wave's own LDS writes are seen by its later LDS reads (in-order per wave); keep the compiler from
+            // moving the reads above them
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            for (int e = lane; e < nmiss; e += 64) {
+                const int slot = wl[e];
+                const unsigned k = nbu[slot];
+                const unsigned ux = k & 0xFFFFu, uy = k >> 16;
+                if (BIG) {  // (levels of 2^30 words or more: 64-bit addresses, one cell of the 2 x 2 at a time -- the
+                            // four address pairs and values at once do not fit the instance's 80 VGPRs)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        nbf[c * CW_MAXN + slot] = cells[cell_word(g, (int)ux + (c & 1), (int)uy + (c >> 1))];
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                } else {
+                    const char *cb = reinterpret_cast<const char *>(cells);
+                    const float l0 = *reinterpret_cast<const float *>(cb + 4u * cell_off(g, ux, uy));
+                    const float l1 = *reinterpret_cast<const float *>(cb + 4u * cell_off(g, ux + 1u, uy));
+                    const float l2 = *reinterpret_cast<const float *>(cb + 4u * cell_off(g, ux, uy + 1u));
+                    const float l3 = *reinterpret_cast<const float *>(cb + 4u * cell_off(g, ux + 1u, uy + 1u));
+                    nbf[0 * CW_MAXN + slot] = l0;
+                    nbf[1 * CW_MAXN + slot] = l1;
+                    nbf[2 * CW_MAXN + slot] = l2;
+                    nbf[3 * CW_MAXN + slot] = l3;
+                }
+            }
             if (lane == 0) s_mcnt[pw] = nmiss;
         }
     }
