@@ -20,9 +20,10 @@
  *
  * ONE sensor only: the node has one laser, so a graph's scans are one sensor's and a scan's state id is its index.
  *
- * Out of scope (the host keeps them): the accept / reject thresholds of TryCloseLoop on response and variance;
- * LinkScans and the optimiser's AddConstraint (the host feeds spa_add_constraint as before); ComputeWeightedMean;
- * the running-scan buffer (AddRunningScan); more than one sensor.  open_karto needs boost, absent from this image,
+ * Out of scope here: the accept / reject thresholds of TryCloseLoop and LinkNearChains on response and variance,
+ * LinkScans with the optimiser's AddConstraint and ComputeWeightedMean are karto_link.h's (ke_*), which consumes
+ * this header's results on the device; the running-scan buffer (AddRunningScan) and more than one sensor stay with
+ * the caller.  open_karto needs boost, absent from this image,
  * so parity with the compiled library is UNPINNED, as for the matcher (karto.h), the grid (karto_grid.h) and the
  * optimiser (spa.h): the results equal the CPU restatement tests/ref/karto_loop_ref.c bit for bit, and that
  * restatement equals a literal transcription of the reference members (tests/ref/karto_loop_plain.py).
