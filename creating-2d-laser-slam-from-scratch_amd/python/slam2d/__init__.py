@@ -7,8 +7,9 @@ from ._lib import LIB_PATH, Slam2dError, build, lib  # noqa: F401
 from .karto_grid import OccupancyGridBuilder  # noqa: F401
 from .karto_link import LinkStage  # noqa: F401
 from .karto_loop import LoopSearchFleet  # noqa: F401
+from .karto_process import ProcessStage  # noqa: F401
 from .spa import SpaFleet, SpaSolver  # noqa: F401
 from .undistort import LidarUndistortion, UndistortFleet  # noqa: F401
 
 __all__ = ["LIB_PATH", "Slam2dError", "build", "lib", "LidarUndistortion", "UndistortFleet", "OccupancyGridBuilder", "SpaFleet",
-           "SpaSolver", "LoopSearchFleet", "LinkStage"]
+           "SpaSolver", "LoopSearchFleet", "LinkStage", "ProcessStage"]

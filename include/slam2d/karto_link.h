@@ -15,8 +15,9 @@
  *   ke_close_device        LinkChainToScan(candidateChain, pScan, bestPose, covariance)       Mapper.cpp:1035
  *   ke_commit              AddEdge's rIsNewEdge deciding LinkScans' AddConstraint             Mapper.cpp:1107-1120
  *
- * Out of scope (the caller keeps them): HasMovedEnough; the running-scan buffer (the caller names the running
- * scans' chain to kl_closest_device); the first-scan linking to other sensors (Mapper.cpp:924-954: one sensor per
+ * Out of scope (the caller keeps them): HasMovedEnough and the running-scan buffer (the caller names the running
+ * scans' chain to kl_closest_device; karto_process.h decides both on the device and writes the ke_job rows and that
+ * chain); the first-scan linking to other sensors (Mapper.cpp:924-954: one sensor per
  * graph); AddVertex / AddNode (the caller's, before AddEdges, as in Mapper::Process); graph edits on the device (the
  * graphs of kl_ctx and spa_ctx are host-mirrored: ke_commit edits them on the host from small fixed-size records).
  * Parity with the compiled library is UNPINNED as for karto_loop.h (open_karto needs boost): the results equal the

@@ -22,8 +22,9 @@
  *
  * Out of scope here: the accept / reject thresholds of TryCloseLoop and LinkNearChains on response and variance,
  * LinkScans with the optimiser's AddConstraint and ComputeWeightedMean are karto_link.h's (ke_*), which consumes
- * this header's results on the device; the running-scan buffer (AddRunningScan) and more than one sensor stay with
- * the caller.  open_karto needs boost, absent from this image,
+ * this header's results on the device; the running-scan buffer (AddRunningScan) is karto_process.h's (kp_*), which
+ * writes the kl_query rows and the running chain's kl_closest_item; more than one sensor stays with the caller.
+ * open_karto needs boost, absent from this image,
  * so parity with the compiled library is UNPINNED, as for the matcher (karto.h), the grid (karto_grid.h) and the
  * optimiser (spa.h): the results equal the CPU restatement tests/ref/karto_loop_ref.c bit for bit, and that
  * restatement equals a literal transcription of the reference members (tests/ref/karto_loop_plain.py).
