@@ -1,0 +1,47 @@
+// karto_graph_mirror.h -- the host mirrors of the two pose graphs (KlGraph of karto_loop_graph.h, SpaGraph of
+// spa_graph.h) rebuilt from a graph's device arrays after device-side edits: the header's counts and the edge /
+// constraint arrays in insertion order are all a mirror needs, since every other list is compile()'s function of
+// them.  Plain C++, no HIP: karto_loop_capi.hip and spa_capi.hip include it, and so does the stand-alone check
+// tests/cpp/karto_graph_mirror_check.cpp (built with -fsanitize=address,undefined).
+#pragma once
+#include <cstddef>
+
+#include "karto_loop_graph.h"
+#include "spa_graph.h"
+
+namespace s2d {
+
+// ends int[n_edges][2]: source, target.  false (the graph is left empty) when an end is no vertex or an edge joins a
+// vertex to itself -- arrays no sequence of AddVertex / AddEdge calls leaves.
+inline bool kl_mirror_rebuild(KlGraph &gr, int n_scans, int n_edges, const int *ends)
+{
+    gr.clear();
+    if (n_scans < 0 || n_edges < 0) return false;
+    for (int e = 0; e < n_edges; ++e) {
+        const int a = ends[2 * e], b = ends[2 * e + 1];
+        if (a < 0 || a >= n_scans || b < 0 || b >= n_scans || a == b) return false;
+    }
+    for (int k = 0; k < n_scans; ++k) gr.add_vertex();
+    for (int e = 0; e < n_edges; ++e) gr.append_edge(ends[2 * e], ends[2 * e + 1]);
+    return true;
+}
+
+// ids int[n_nodes], poses double[n_nodes][3] (the device's current poses), ends int[n_cons][2] (node indices),
+// means double[n_cons][3], precs double[n_cons][9].  false (the graph is left empty) when an end is no node or a
+// constraint joins a node to itself.
+inline bool spa_mirror_rebuild(SpaGraph &gr, int n_nodes, const int *ids, const double *poses, int n_cons, const int *ends,
+                               const double *means, const double *precs)
+{
+    gr.clear();
+    if (n_nodes < 0 || n_cons < 0) return false;
+    for (int c = 0; c < n_cons; ++c) {
+        const int a = ends[2 * c], b = ends[2 * c + 1];
+        if (a < 0 || a >= n_nodes || b < 0 || b >= n_nodes || a == b) return false;
+    }
+    for (int k = 0; k < n_nodes; ++k) gr.add_node(ids[k], poses + (size_t)3 * k);
+    for (int c = 0; c < n_cons; ++c)
+        gr.add_constraint_by_index(ends[2 * c], ends[2 * c + 1], means + (size_t)3 * c, precs + (size_t)9 * c);
+    return true;
+}
+
+}  // namespace s2d

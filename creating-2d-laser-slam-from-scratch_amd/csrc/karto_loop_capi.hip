@@ -14,6 +14,7 @@
 
 #include "host_timing.h"
 #include "karto_internal.h"  // parse_knob_int (SLAM2D_POISON)
+#include "karto_graph_mirror.h"
 #include "karto_loop_graph.h"
 #include "karto_loop_kernels.hip"
 
@@ -42,9 +43,9 @@ constexpr int KL_MAX_GRAPHS = 1 << 16;
 constexpr int KL_MAX_EDGES = 1 << 20;
 constexpr int KL_MAX_QUERIES = 1 << 20;
 
-enum { L_REFERENCE, L_SEARCH, L_CLOSEST, L_EMIT_SCAN, L_EMIT_WRITE, L_NUM };
+enum { L_REFERENCE, L_SEARCH, L_CLOSEST, L_EMIT_SCAN, L_EMIT_WRITE, L_EDIT_VERTICES, L_EDIT_EDGES, L_NUM };
 const char *const l_names[L_NUM] = {"kl_reference_kernel", "kl_search_kernel", "kl_closest_kernel", "kl_emit_scan_kernel",
-                                    "kl_emit_write_kernel"};
+                                    "kl_emit_write_kernel", "kl_edit_vertices_kernel", "kl_edit_edges_kernel"};
 static_assert(L_NUM <= KernelTimer::MAX_KERNELS, "the timer's accumulators");
 }  // namespace
 
@@ -56,6 +57,11 @@ struct kl_ctx {
     std::vector<int> pool_offset;
     std::vector<char> dirty;  // per graph: edited since the last upload
     bool any_dirty = false;
+    // device edits: a graph's host copy is current only while synced[g] == edit_epoch, which every edit call bumps
+    unsigned edit_epoch = 0, edit_seq = 0;
+    std::vector<unsigned> synced;
+    int2 *d_ends = nullptr;
+    unsigned long long *d_edit_info = nullptr;  // ge_refuse
     KlDev dev{};
     KlHdr *d_hdr = nullptr;
     int *d_adj_off = nullptr;
@@ -110,6 +116,8 @@ int upload_graph(kl_ctx *c, int g)
     const KlHdr h{gr.n_scans(), gr.n_edges(), c->pool_offset[g], 0};
     LCHK(hipMemcpy(c->d_hdr + g, &h, sizeof(h), hipMemcpyHostToDevice));
     LCHK(hipMemcpy(c->d_adj_off + g * (N + 1), gr.adj_off.data(), sizeof(int) * (gr.n_scans() + 1), hipMemcpyHostToDevice));
+    if (!gr.ends.empty())
+        LCHK(hipMemcpy(c->d_ends + g * M, gr.ends.data(), sizeof(int) * gr.ends.size(), hipMemcpyHostToDevice));
     if (!gr.adj.empty())
         LCHK(hipMemcpy(c->d_adj + g * 2 * M, gr.adj.data(), sizeof(int) * gr.adj.size(), hipMemcpyHostToDevice));
     c->dirty[g] = 0;
@@ -125,6 +133,40 @@ int upload_dirty(kl_ctx *c)
         if (c->dirty[g] && (rc = upload_graph(c, g)) != KL_OK) return rc;
     c->any_dirty = false;
     return KL_OK;
+}
+
+// The host copy of graph g, current again after device edits: waits, and copies the header and the edge list back.
+int pull_graph(kl_ctx *c, int g)
+{
+    if (c->synced[g] == c->edit_epoch) return KL_OK;
+    int rc = wait_last(c);
+    if (rc != KL_OK) return rc;
+    KlHdr h{};
+    LCHK(hipMemcpy(&h, c->d_hdr + g, sizeof(h), hipMemcpyDeviceToHost));
+    if (h.n_scans < 0 || h.n_scans > c->N || h.n_edges < 0 || h.n_edges > c->M)
+        return lfail(KL_EHIP, "the device header of the graph is out of range");
+    std::vector<int> ends((size_t)h.n_edges * 2);
+    if (h.n_edges > 0)
+        LCHK(hipMemcpy(ends.data(), c->d_ends + (size_t)g * c->M, sizeof(int) * ends.size(), hipMemcpyDeviceToHost));
+    if (!kl_mirror_rebuild(c->graphs[g], h.n_scans, h.n_edges, ends.data()))
+        return lfail(KL_EHIP, "the device edge list of the graph is not a graph's");
+    c->synced[g] = c->edit_epoch;
+    return KL_OK;
+}
+
+KlEdit edit_args(kl_ctx *c)
+{
+    return KlEdit{c->d_hdr, c->d_adj_off, c->d_adj, c->d_ends, c->d_edit_info, c->N, c->M, c->G, c->edit_seq};
+}
+
+// before a device edit: pending host edits go up (the only wait); afterwards every host copy is behind
+int begin_edit(kl_ctx *c, hipStream_t s)
+{
+    int rc = upload_dirty(c);
+    if (rc != KL_OK) return rc;
+    ++c->edit_epoch;
+    ++c->edit_seq;
+    return begin_on(c, s);
 }
 
 void touch(kl_ctx *c, int g)
@@ -199,7 +241,7 @@ int kl_destroy(kl_ctx *c)
     if (!c) return KL_OK;
     if (c->last) hipStreamSynchronize(c->last);
     if (c->stream) hipStreamSynchronize(c->stream);
-    void *bufs[] = {c->d_hdr, c->d_adj_off, c->d_adj, c->dev.ref, c->dev.res, c->dev.queries, c->dev.d2,
+    void *bufs[] = {c->d_ends, c->d_edit_info, c->d_hdr, c->d_adj_off, c->d_adj, c->dev.ref, c->dev.res, c->dev.queries, c->dev.d2,
                     c->dev.near_link, c->dev.near_loop, c->dev.loop_chains, c->dev.near_chains, c->dev.emit_off,
                     c->dev.emit_info, c->d_qin, c->d_ranges, c->d_poses};
     for (void *b : bufs)
@@ -243,6 +285,7 @@ int kl_create(kl_ctx **out, const kt_laser *laser, const kl_params *params, int 
     c->graphs.resize((size_t)max_graphs);
     c->pool_offset.assign((size_t)max_graphs, 0);
     c->dirty.assign((size_t)max_graphs, 0);
+    c->synced.assign((size_t)max_graphs, 0);
     c->lds = kl_search_lds(max_scans);
     hipError_t e;
     if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamDefault)) != hipSuccess ||
@@ -278,6 +321,8 @@ int kl_create(kl_ctx **out, const kt_laser *laser, const kl_params *params, int 
     LALLOC(c->d_hdr, sizeof(KlHdr) * G);
     LALLOC(c->d_adj_off, sizeof(int) * G * (N + 1));
     LALLOC(c->d_adj, sizeof(int2) * G * 2 * M);
+    LALLOC(c->d_ends, sizeof(int2) * G * M);
+    LALLOC(c->d_edit_info, sizeof(unsigned long long) * 2);
     LALLOC(d.ref, sizeof(double2) * G * N);
     LALLOC(d.res, sizeof(kl_result) * Q);
     LALLOC(d.queries, sizeof(kl_query) * Q);
@@ -301,6 +346,8 @@ int kl_create(kl_ctx **out, const kt_laser *laser, const kl_params *params, int 
     }
     if ((e = hipMemsetAsync(c->d_hdr, 0, sizeof(KlHdr) * G, c->stream)) != hipSuccess ||
         (e = hipMemsetAsync(d.emit_info, 0, sizeof(int) * 2, c->stream)) != hipSuccess ||
+        (e = hipMemsetAsync(c->d_edit_info, 0, sizeof(unsigned long long), c->stream)) != hipSuccess ||
+        (e = hipMemsetAsync(c->d_edit_info + 1, 0xff, sizeof(unsigned long long), c->stream)) != hipSuccess ||
         (e = hipMemcpyAsync(d.res, r0.data(), sizeof(kl_result) * Q, hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
         (e = hipStreamSynchronize(c->stream)) != hipSuccess ||
         (e = hipEventRecord(c->ev_last, c->stream)) != hipSuccess) {
@@ -316,6 +363,7 @@ int kl_add_vertex(kl_ctx *c, int g, int *state_id)
     int rc = check_graph(c, g);
     if (rc != KL_OK) return rc;
     std::lock_guard<std::mutex> lock(c->mu);
+    if ((rc = pull_graph(c, g)) != KL_OK) return rc;
     if (c->graphs[g].n_scans() >= c->N) return lfail(KL_ERANGE, "the graph already has max_scans scans");
     const int id = c->graphs[g].add_vertex();
     if (state_id) *state_id = id;
@@ -329,6 +377,7 @@ int kl_add_edge(kl_ctx *c, int g, int source, int target, int *is_new)
     int rc = check_graph(c, g);
     if (rc != KL_OK) return rc;
     std::lock_guard<std::mutex> lock(c->mu);
+    if ((rc = pull_graph(c, g)) != KL_OK) return rc;
     KlGraph &gr = c->graphs[g];
     if (source < 0 || source >= gr.n_scans() || target < 0 || target >= gr.n_scans())
         return lfail(KL_EINVAL, "edge end is not a vertex of the graph");
@@ -358,6 +407,7 @@ int kl_set_graph(kl_ctx *c, int g, int n_scans, int n_edges, const int *ends)
     gr.clear();
     for (int k = 0; k < n_scans; ++k) gr.add_vertex();
     for (int e = 0; e < n_edges; ++e) gr.append_edge(ends[2 * e], ends[2 * e + 1]);
+    c->synced[g] = c->edit_epoch;
     touch(c, g);
     return KL_OK;
 }
@@ -368,6 +418,7 @@ int kl_clear_graph(kl_ctx *c, int g)
     if (rc != KL_OK) return rc;
     std::lock_guard<std::mutex> lock(c->mu);
     c->graphs[g].clear();
+    c->synced[g] = c->edit_epoch;
     touch(c, g);
     return KL_OK;
 }
@@ -377,6 +428,7 @@ int kl_get_counts(kl_ctx *c, int g, int *n_scans, int *n_edges)
     int rc = check_graph(c, g);
     if (rc != KL_OK) return rc;
     std::lock_guard<std::mutex> lock(c->mu);
+    if ((rc = pull_graph(c, g)) != KL_OK) return rc;
     if (n_scans) *n_scans = c->graphs[g].n_scans();
     if (n_edges) *n_edges = c->graphs[g].n_edges();
     return KL_OK;
@@ -388,6 +440,7 @@ int kl_set_pool_offset(kl_ctx *c, int g, int offset)
     if (rc != KL_OK) return rc;
     if (offset < 0 || offset > INT_MAX - KL_MAX_SCANS) return lfail(KL_EINVAL, "pool offset out of range");
     std::lock_guard<std::mutex> lock(c->mu);
+    if ((rc = pull_graph(c, g)) != KL_OK) return rc;  // the upload that follows rewrites the whole graph
     c->pool_offset[g] = offset;
     touch(c, g);
     return KL_OK;
@@ -576,6 +629,80 @@ int kl_get_emit_info(kl_ctx *c, int *total_matches, int *status)
     LCHK(hipMemcpy(info, c->dev.emit_info, sizeof(info), hipMemcpyDeviceToHost));
     if (total_matches) *total_matches = info[0];
     if (status) *status = info[1];
+    return KL_OK;
+}
+
+int kl_edit_vertices_device(kl_ctx *c, int count, const int *d_graph, const int *d_expect_id, int *d_id_out,
+                            int *d_status_out, void *hip_stream)
+{
+    if (!c) return lfail(KL_EINVAL, "ctx is NULL");
+    if (count < 0) return lfail(KL_EINVAL, "negative count");
+    if (count == 0) return KL_OK;
+    if (!d_graph) return lfail(KL_EINVAL, "d_graph is NULL");
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    int rc = begin_edit(c, s);
+    if (rc != KL_OK) return rc;
+    KL_LAUNCH(L_EDIT_VERTICES, kl_edit_vertices_kernel, dim3((unsigned)count), dim3(GE_THREADS), 0, s, edit_args(c), count,
+              d_graph, d_expect_id, d_id_out, d_status_out);
+    return end_on(c, s);
+}
+
+int kl_edit_edges_device(kl_ctx *c, int count, const kl_edge_row *d_rows, int *d_is_new_out, int *d_status_out,
+                         void *hip_stream)
+{
+    if (!c) return lfail(KL_EINVAL, "ctx is NULL");
+    if (count < 0) return lfail(KL_EINVAL, "negative count");
+    if (count == 0) return KL_OK;
+    if (!d_rows) return lfail(KL_EINVAL, "d_rows is NULL");
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    int rc = begin_edit(c, s);
+    if (rc != KL_OK) return rc;
+    const size_t lds = sizeof(int) * ((size_t)c->N + 1 + GE_THREADS + GE_WAVES + 1);
+    KL_LAUNCH(L_EDIT_EDGES, kl_edit_edges_kernel, dim3((unsigned)count), dim3(GE_THREADS), lds, s, edit_args(c), count,
+              d_rows, d_is_new_out, d_status_out);
+    return end_on(c, s);
+}
+
+int kl_get_edit_info(kl_ctx *c, int *n_refused, int *first_status)
+{
+    if (!c) return lfail(KL_EINVAL, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(c->mu);
+    int rc = wait_last(c);
+    if (rc != KL_OK) return rc;
+    unsigned long long info[2] = {0, 0};
+    LCHK(hipMemcpy(info, c->d_edit_info, sizeof(info), hipMemcpyDeviceToHost));
+    if (n_refused) *n_refused = (int)info[0];
+    if (first_status) *first_status = info[0] ? -(int)(info[1] & 0xff) : KL_OK;
+    const unsigned long long fresh[2] = {0, ~0ull};
+    LCHK(hipMemcpy(c->d_edit_info, fresh, sizeof(fresh), hipMemcpyHostToDevice));
+    c->edit_seq = 0;
+    return KL_OK;
+}
+
+int kl_download_graph(kl_ctx *c, int g, int *n_scans, int *n_edges, int *ends_out, int *adj_off_out, int *adj_out)
+{
+    int rc = check_graph(c, g);
+    if (rc != KL_OK) return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if ((rc = upload_dirty(c)) != KL_OK) return rc;
+    if ((rc = wait_last(c)) != KL_OK) return rc;
+    KlHdr h{};
+    LCHK(hipMemcpy(&h, c->d_hdr + g, sizeof(h), hipMemcpyDeviceToHost));
+    if (h.n_scans < 0 || h.n_scans > c->N || h.n_edges < 0 || h.n_edges > c->M)
+        return lfail(KL_EHIP, "the device header of the graph is out of range");
+    if (n_scans) *n_scans = h.n_scans;
+    if (n_edges) *n_edges = h.n_edges;
+    const size_t N = (size_t)c->N, M = (size_t)c->M;
+    if (ends_out && h.n_edges > 0)
+        LCHK(hipMemcpy(ends_out, c->d_ends + g * M, sizeof(int2) * h.n_edges, hipMemcpyDeviceToHost));
+    if (adj_off_out) {
+        if (h.n_scans > 0) LCHK(hipMemcpy(adj_off_out, c->d_adj_off + g * (N + 1), sizeof(int) * (h.n_scans + 1), hipMemcpyDeviceToHost));
+        else adj_off_out[0] = 0;  // a graph without scans has no list on the device
+    }
+    if (adj_out && h.n_edges > 0)
+        LCHK(hipMemcpy(adj_out, c->d_adj + g * 2 * M, sizeof(int2) * 2 * h.n_edges, hipMemcpyDeviceToHost));
     return KL_OK;
 }
 

@@ -18,6 +18,7 @@
 //                        GetClosestScanToPose per near chain by one wave.
 //   kl_closest_kernel    one wave per (scan, chain): GetClosestScanToPose and LinkChainToScan's distance test.
 //   kl_emit_scan_kernel / kl_emit_write_kernel  the chains of a search as kt_match_batch_device's arrays.
+//   kl_edit_vertices_kernel / kl_edit_edges_kernel  AddVertex / AddEdge on the device, and the adjacency rebuilt.
 // All arithmetic is double with -ffp-contract=off and detmath.h's sin / cos; no float atomics anywhere.  The CPU
 // restatement tests/ref/karto_loop_ref.c gives the same bits.
 #include <hip/hip_runtime.h>
@@ -27,6 +28,7 @@
 
 #include "../../include/slam2d/karto_loop.h"
 #include "detmath.h"
+#include "graph_edit_device.h"
 
 namespace s2d {
 
@@ -569,6 +571,146 @@ kl_emit_write_kernel(KlDev D, int which, int capacity, int *__restrict__ query_o
         ++mi;
         ii += l;
     }
+}
+
+// =================================================================================================
+// kl_edit_vertices_kernel / kl_edit_edges_kernel: AddVertex and AddEdge on the device (graph_edit_device.h: one
+// workgroup per row, the first row of a graph leads it).  Wave 0 of the leader applies the graph's rows in row order;
+// AddEdge's lookup runs over the source's adjacency as uploaded or rebuilt (all 64 lanes: an entry (other end, e)
+// matches when ends[e].y is the target) and over the edges this call has appended so far.  Then all lanes rebuild the
+// adjacency from the edge list by a stable bucket fill over the 2m edge ends, which is KlGraph::compile()'s order.
+// LDS of the edges kernel: (max_scans + 1 + GE_THREADS + GE_WAVES + 1) ints.
+// =================================================================================================
+struct KlEdit {
+    KlHdr *hdr;
+    int *adj_off;
+    int2 *adj;
+    int2 *ends;                // [G][max_edges]: source, target, in insertion order
+    unsigned long long *info;  // ge_refuse
+    int max_scans, max_edges, G;
+    unsigned seq;
+};
+
+__global__ void __launch_bounds__(GE_THREADS)
+kl_edit_vertices_kernel(KlEdit E, int count, const int *__restrict__ graph, const int *__restrict__ expect,
+                        int *__restrict__ id_out, int *__restrict__ status_out)
+{
+    const int row = blockIdx.x, lane = threadIdx.x & 63;
+    const int g = graph[row];
+    if (g < 0 || g >= E.G) {
+        if (threadIdx.x == 0) {
+            if (id_out) id_out[row] = -1;
+            if (status_out) status_out[row] = g < 0 ? KL_OK : KL_EINVAL;
+            if (g >= 0) ge_refuse(E.info, E.seq, row, KL_EINVAL);
+        }
+        return;
+    }
+    if (!ge_is_leader(graph, sizeof(int), row, g)) return;
+    if (threadIdx.x >= 64) return;  // wave 0 alone from here: no workgroup barrier below
+    const int n0 = E.hdr[g].n_scans;
+    int n = n0;
+    for (int base = row; base < count; base += 64) {
+        const int j = base + lane;
+        unsigned long long mask = __ballot(j < count && graph[j] == g);
+        while (mask) {
+            const int r = base + __ffsll((long long)mask) - 1;
+            mask &= mask - 1;
+            const int ex = expect ? expect[r] : -1;
+            int st = KL_OK, id = -1;
+            if (ex >= 0 && ex != n) st = KL_EINVAL;
+            else if (n >= E.max_scans) st = KL_ERANGE;
+            else id = n++;
+            if (lane == 0) {
+                if (id_out) id_out[r] = id;
+                if (status_out) status_out[r] = st;
+                if (st != KL_OK) ge_refuse(E.info, E.seq, r, st);
+            }
+        }
+    }
+    if (n == n0) return;
+    int *off = E.adj_off + (size_t)g * (E.max_scans + 1);
+    const int end = n0 > 0 ? off[n0] : 0;  // a graph never uploaded has no offset yet
+    for (int k = (n0 > 0 ? n0 + 1 : 0) + lane; k <= n; k += 64) off[k] = end;
+    if (lane == 0) E.hdr[g].n_scans = n;
+}
+
+__global__ void __launch_bounds__(GE_THREADS)
+kl_edit_edges_kernel(KlEdit E, int count, const kl_edge_row *__restrict__ rows, int *__restrict__ is_new_out,
+                     int *__restrict__ status_out)
+{
+    extern __shared__ int kl_edit_smem[];
+    int *cur = kl_edit_smem, *s_b = cur + E.max_scans + 1, *sw = s_b + GE_THREADS, *s_m = sw + GE_WAVES;
+    const int row = blockIdx.x, lane = threadIdx.x & 63;
+    const int g = rows[row].graph;
+    if (g < 0 || g >= E.G) {
+        if (threadIdx.x == 0) {
+            if (is_new_out) is_new_out[row] = 0;
+            if (status_out) status_out[row] = g < 0 ? KL_OK : KL_EINVAL;
+            if (g >= 0) ge_refuse(E.info, E.seq, row, KL_EINVAL);
+        }
+        return;
+    }
+    if (!ge_is_leader(rows, sizeof(kl_edge_row), row, g)) return;
+    const KlHdr h = E.hdr[g];
+    const int n = h.n_scans, m0 = h.n_edges;
+    int *off = E.adj_off + (size_t)g * (E.max_scans + 1);
+    int2 *adj = E.adj + (size_t)g * 2 * E.max_edges;
+    int2 *ends = E.ends + (size_t)g * E.max_edges;
+    if (threadIdx.x < 64) {
+        int m = m0;
+        for (int base = row; base < count; base += 64) {
+            const int j = base + lane;
+            unsigned long long mask = __ballot(j < count && rows[j].graph == g);
+            while (mask) {
+                const int r = base + __ffsll((long long)mask) - 1;
+                mask &= mask - 1;
+                const int s = rows[r].source, t = rows[r].target;
+                int st = KL_OK, nw = 0;
+                if (s < 0 || s >= n || t < 0 || t >= n || s == t) {
+                    st = KL_EINVAL;
+                } else {
+                    int found = 0;
+                    const int a1 = off[s + 1];
+                    for (int k = off[s] + lane; k < a1; k += 64) found |= ends[adj[k].y].y == t;
+                    for (int e = m0 + lane; e < m; e += 64) {
+                        const int2 ee = ends[e];
+                        found |= ee.x == s && ee.y == t;
+                    }
+                    if (__ballot(found) == 0) {
+                        if (m >= E.max_edges) {
+                            st = KL_ERANGE;
+                        } else {
+                            if (lane == 0) ends[m] = make_int2(s, t);
+                            ++m;
+                            nw = 1;
+                            ge_fence();
+                        }
+                    }
+                }
+                if (lane == 0) {
+                    if (is_new_out) is_new_out[r] = nw;
+                    if (status_out) status_out[r] = st;
+                    if (st != KL_OK) ge_refuse(E.info, E.seq, r, st);
+                }
+            }
+        }
+        if (lane == 0) *s_m = m;
+    }
+    __threadfence_block();
+    __syncthreads();
+    const int m = *s_m;
+    if (m == m0) return;
+    ge_bucket_fill(
+        n, 2 * m, cur, s_b, sw, off,
+        [&](int x) {
+            const int2 e = ends[x >> 1];
+            return (x & 1) ? e.y : e.x;
+        },
+        [&](int x, int pos) {
+            const int2 e = ends[x >> 1];
+            adj[pos] = make_int2((x & 1) ? e.x : e.y, x >> 1);
+        });
+    if (threadIdx.x == 0) E.hdr[g].n_edges = m;
 }
 
 }  // namespace s2d

@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "karto_graph_mirror.h"
 #include "spa_graph.h"
 #include "spa_kernels.hip"
 
@@ -47,6 +48,11 @@ struct spa_ctx {
     std::vector<int> uploaded_nodes;  // per graph: nodes [0, uploaded) have their pose on the device
     std::vector<char> dirty;          // per graph: edited since the last upload
     std::vector<int> n_fixed;         // per graph: SysSPA2d::nFixed, or SPA_FIXED_FROM_PARAMS
+    // device edits: a graph's host copy is current only while synced[g] == edit_epoch, which every edit call bumps
+    unsigned edit_epoch = 0, edit_seq = 0;
+    std::vector<unsigned> synced;
+    int *d_ids = nullptr;
+    unsigned long long *d_edit_info = nullptr;  // ge_refuse
     SpaDev dev{};
     SpaHdr *d_hdr = nullptr;
     int2 *d_con_nd = nullptr, *d_nbr = nullptr;
@@ -90,6 +96,7 @@ int upload_graph(spa_ctx *c, int g)
         SCHK(hipMemcpy(c->dev.poses + (g * N + up) * 3, gr.poses.data() + (size_t)up * 3, sizeof(double) * 3 * (n - up),
                        hipMemcpyHostToDevice));
     c->uploaded_nodes[g] = n;
+    if (n > 0) SCHK(hipMemcpy(c->d_ids + g * N, gr.ids.data(), sizeof(int) * n, hipMemcpyHostToDevice));
     if (m > 0) {
         SCHK(hipMemcpy(c->d_con_nd + g * M, gr.ends.data(), sizeof(int) * 2 * m, hipMemcpyHostToDevice));
         SCHK(hipMemcpy(c->d_con_mean + g * M * 3, gr.means.data(), sizeof(double) * 3 * m, hipMemcpyHostToDevice));
@@ -104,6 +111,68 @@ int upload_graph(spa_ctx *c, int g)
     SCHK(hipMemcpy(c->d_pair_off + g * (M + 1), gr.pair_off.data(), sizeof(int) * gr.pair_off.size(),
                    hipMemcpyHostToDevice));
     c->dirty[g] = 0;
+    return SPA_OK;
+}
+
+// The host copy of graph g, current again after device edits: waits, and copies the header, the nodes and the
+// constraints back.  The poses of the copy are the device's current ones, and all of them count as uploaded.
+int pull_graph(spa_ctx *c, int g)
+{
+    if (c->synced[g] == c->edit_epoch) return SPA_OK;
+    int rc = wait_last(c);
+    if (rc != SPA_OK) return rc;
+    const size_t N = (size_t)c->N, M = (size_t)c->M;
+    SpaHdr h{};
+    SCHK(hipMemcpy(&h, c->d_hdr + g, sizeof(h), hipMemcpyDeviceToHost));
+    if (h.n_nodes < 0 || h.n_nodes > c->N || h.n_cons < 0 || h.n_cons > c->M)
+        return sfail(SPA_EHIP, "the device header of the graph is out of range");
+    const size_t n = (size_t)h.n_nodes, m = (size_t)h.n_cons;
+    std::vector<int> ids(n), ends(2 * m);
+    std::vector<double> poses(3 * n), means(3 * m), precs(9 * m);
+    if (n > 0) {
+        SCHK(hipMemcpy(ids.data(), c->d_ids + g * N, sizeof(int) * n, hipMemcpyDeviceToHost));
+        SCHK(hipMemcpy(poses.data(), c->dev.poses + g * N * 3, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
+    }
+    if (m > 0) {
+        SCHK(hipMemcpy(ends.data(), c->d_con_nd + g * M, sizeof(int) * 2 * m, hipMemcpyDeviceToHost));
+        SCHK(hipMemcpy(means.data(), c->d_con_mean + g * M * 3, sizeof(double) * 3 * m, hipMemcpyDeviceToHost));
+        SCHK(hipMemcpy(precs.data(), c->d_con_prec + g * M * 9, sizeof(double) * 9 * m, hipMemcpyDeviceToHost));
+    }
+    if (!spa_mirror_rebuild(c->graphs[g], h.n_nodes, ids.data(), poses.data(), h.n_cons, ends.data(), means.data(),
+                            precs.data()))
+        return sfail(SPA_EHIP, "the device constraint list of the graph is not a graph's");
+    c->graphs[g].compile();  // spa_envelope_blocks reads the lists of a graph that is not dirty
+    c->uploaded_nodes[g] = h.n_nodes;
+    c->synced[g] = c->edit_epoch;
+    return SPA_OK;
+}
+
+SpaEdit edit_args(spa_ctx *c)
+{
+    return SpaEdit{c->d_hdr,   c->dev.poses, c->d_ids,      c->d_con_nd,   c->d_con_mean,    c->d_con_prec,
+                   c->d_inc_off, c->d_inc,   c->d_nbr_off,  c->d_nbr,      c->d_pair_off,    c->d_pair_con,
+                   c->dev.scratch, c->d_edit_info, c->N,    c->M,          c->G,             c->edit_seq};
+}
+
+// before a device edit: the context's sizes, then pending host edits go up (the only wait); afterwards every host
+// copy is behind
+int begin_edit(spa_ctx *c, hipStream_t s)
+{
+    if (c->N > SPA_EDIT_MAX_NODES) return sfail(SPA_ERANGE, "device edits need max_nodes <= SPA_EDIT_MAX_NODES (4096)");
+    int rc;
+    for (int g = 0; g < c->G; ++g)
+        if (c->dirty[g] && (rc = upload_graph(c, g)) != SPA_OK) return rc;
+    ++c->edit_epoch;
+    ++c->edit_seq;
+    SCHK(hipStreamWaitEvent(s, c->ev_last, 0));
+    return SPA_OK;
+}
+
+int end_edit(spa_ctx *c, hipStream_t s)
+{
+    SCHK(hipGetLastError());
+    SCHK(hipEventRecord(c->ev_last, s));
+    c->last = s;
     return SPA_OK;
 }
 
@@ -185,6 +254,7 @@ int spa_create_ex(spa_ctx **out, int max_graphs, int max_nodes, int max_constrai
     c->graphs.resize((size_t)max_graphs);
     c->uploaded_nodes.assign((size_t)max_graphs, 0);
     c->dirty.assign((size_t)max_graphs, 1);
+    c->synced.assign((size_t)max_graphs, 0);
     c->n_fixed.assign((size_t)max_graphs, SPA_FIXED_FROM_PARAMS);
     const size_t G = (size_t)max_graphs, N = (size_t)max_nodes, M = (size_t)max_constraints;
     c->scratch_bytes = sizeof(double) * G * spa_scratch_doubles(max_nodes, max_constraints);
@@ -198,6 +268,8 @@ int spa_create_ex(spa_ctx **out, int max_graphs, int max_nodes, int max_constrai
     }
     if ((e = hipMalloc(&c->d_hdr, sizeof(SpaHdr) * G)) != hipSuccess ||
         (e = hipMalloc(&c->dev.poses, sizeof(double) * G * N * 3)) != hipSuccess ||
+        (e = hipMalloc(&c->d_ids, sizeof(int) * G * N)) != hipSuccess ||
+        (e = hipMalloc(&c->d_edit_info, sizeof(unsigned long long) * 2)) != hipSuccess ||
         (e = hipMalloc(&c->d_con_nd, sizeof(int2) * G * M)) != hipSuccess ||
         (e = hipMalloc(&c->d_con_mean, sizeof(double) * G * M * 3)) != hipSuccess ||
         (e = hipMalloc(&c->d_con_prec, sizeof(double) * G * M * 9)) != hipSuccess ||
@@ -234,6 +306,8 @@ int spa_create_ex(spa_ctx **out, int max_graphs, int max_nodes, int max_constrai
     }
     if ((e = hipMemcpy(c->dev.stats, st.data(), sizeof(spa_stats) * G, hipMemcpyHostToDevice)) != hipSuccess ||
         (e = hipMemset(c->dev.poses, 0, sizeof(double) * G * N * 3)) != hipSuccess ||
+        (e = hipMemset(c->d_edit_info, 0, sizeof(unsigned long long))) != hipSuccess ||
+        (e = hipMemset(c->d_edit_info + 1, 0xff, sizeof(unsigned long long))) != hipSuccess ||
         (e = hipEventRecord(c->ev_last, c->stream)) != hipSuccess) {
         spa_destroy(c);
         return sfail(SPA_EHIP, "initialising the context", e);
@@ -247,7 +321,7 @@ int spa_destroy(spa_ctx *c)
     if (!c) return SPA_OK;
     if (c->last) hipStreamSynchronize(c->last);
     if (c->stream) hipStreamSynchronize(c->stream);
-    void *bufs[] = {c->d_hdr, c->dev.poses, c->d_con_nd, c->d_con_mean, c->d_con_prec, c->d_inc_off, c->d_inc,
+    void *bufs[] = {c->d_ids, c->d_edit_info, c->d_hdr, c->dev.poses, c->d_con_nd, c->d_con_mean, c->d_con_prec, c->d_inc_off, c->d_inc,
                     c->d_nbr_off, c->d_nbr, c->d_pair_off, c->d_pair_con, c->dev.scratch, c->dev.stats, c->dev.fac,
                     c->dev.fidx};
     for (void *b : bufs)
@@ -264,6 +338,7 @@ int spa_add_node(spa_ctx *c, int g, int id, const double *pose)
     if (rc != SPA_OK) return rc;
     if (!pose) return sfail(SPA_EINVAL, "pose is NULL");
     std::lock_guard<std::mutex> lock(c->mu);
+    if ((rc = pull_graph(c, g)) != SPA_OK) return rc;
     if (c->graphs[g].n_nodes() >= c->N) return sfail(SPA_ERANGE, "the graph already has max_nodes nodes");
     c->graphs[g].add_node(id, pose);
     c->dirty[g] = 1;
@@ -278,6 +353,7 @@ int spa_add_constraint(spa_ctx *c, int g, int id0, int id1, const double *mean, 
     if (!mean || !prec) return sfail(SPA_EINVAL, "NULL argument");
     if (id0 == id1) return sfail(SPA_EINVAL, "a constraint from a node to itself");
     std::lock_guard<std::mutex> lock(c->mu);
+    if ((rc = pull_graph(c, g)) != SPA_OK) return rc;
     SpaGraph &gr = c->graphs[g];
     const int ni0 = gr.find(id0), ni1 = gr.find(id1);
     if (ni0 < 0 || ni1 < 0) return SPA_OK;  // addConstraint returns false (:241)
@@ -309,6 +385,7 @@ int spa_set_graph(spa_ctx *c, int g, int n_nodes, const int *ids, const double *
     for (int k = 0; k < n_nodes; ++k) gr.add_node(ids[k], poses + 3 * k);
     for (int ci = 0; ci < n_cons; ++ci) gr.add_constraint_by_index(ends[2 * ci], ends[2 * ci + 1], means + 3 * ci, precs + 9 * ci);
     c->uploaded_nodes[g] = 0;
+    c->synced[g] = c->edit_epoch;
     c->dirty[g] = 1;
     return SPA_OK;
 }
@@ -320,6 +397,7 @@ int spa_clear_graph(spa_ctx *c, int g)
     std::lock_guard<std::mutex> lock(c->mu);
     c->graphs[g].clear();
     c->uploaded_nodes[g] = 0;
+    c->synced[g] = c->edit_epoch;
     c->dirty[g] = 1;
     return SPA_OK;
 }
@@ -329,6 +407,7 @@ int spa_set_n_fixed(spa_ctx *c, int g, int n_fixed)
     int rc = check_graph(c, g);
     if (rc != SPA_OK) return rc;
     std::lock_guard<std::mutex> lock(c->mu);
+    if ((rc = pull_graph(c, g)) != SPA_OK) return rc;  // the upload that follows rewrites the whole graph
     c->n_fixed[g] = n_fixed;
     c->dirty[g] = 1;
     return SPA_OK;
@@ -339,6 +418,7 @@ int spa_get_counts(spa_ctx *c, int g, int *n_nodes, int *n_cons)
     int rc = check_graph(c, g);
     if (rc != SPA_OK) return rc;
     std::lock_guard<std::mutex> lock(c->mu);
+    if ((rc = pull_graph(c, g)) != SPA_OK) return rc;
     if (n_nodes) *n_nodes = c->graphs[g].n_nodes();
     if (n_cons) *n_cons = c->graphs[g].n_cons();
     return SPA_OK;
@@ -350,6 +430,7 @@ int spa_envelope_blocks(spa_ctx *c, int g, int n_fixed, long long *blocks)
     if (rc != SPA_OK) return rc;
     if (!blocks) return sfail(SPA_EINVAL, "blocks is NULL");
     std::lock_guard<std::mutex> lock(c->mu);
+    if ((rc = pull_graph(c, g)) != SPA_OK) return rc;
     SpaGraph &gr = c->graphs[g];
     if (c->dirty[g]) gr.compile();  // the lists only; the upload stays with the next compute
     *blocks = gr.envelope_blocks(n_fixed);
@@ -379,6 +460,7 @@ int spa_get_nodes(spa_ctx *c, int g, int *ids_out, double *poses_out)
     if (rc != SPA_OK) return rc;
     std::lock_guard<std::mutex> lock(c->mu);
     if ((rc = wait_last(c)) != SPA_OK) return rc;
+    if ((rc = pull_graph(c, g)) != SPA_OK) return rc;
     const SpaGraph &gr = c->graphs[g];
     const int n = gr.n_nodes(), up = c->uploaded_nodes[g];
     if (ids_out)
@@ -397,6 +479,7 @@ int spa_device_poses(spa_ctx *c, int g, const double **d_poses, int *n)
     int rc = check_graph(c, g);
     if (rc != SPA_OK) return rc;
     std::lock_guard<std::mutex> lock(c->mu);
+    if ((rc = pull_graph(c, g)) != SPA_OK) return rc;
     if (c->dirty[g] && (rc = upload_graph(c, g)) != SPA_OK) return rc;  // nodes added since the last compute
     if (d_poses) *d_poses = c->dev.poses + (size_t)g * c->N * 3;
     if (n) *n = c->graphs[g].n_nodes();
@@ -411,6 +494,95 @@ int spa_get_stats(spa_ctx *c, int g, spa_stats *stats)
     std::lock_guard<std::mutex> lock(c->mu);
     if ((rc = wait_last(c)) != SPA_OK) return rc;
     SCHK(hipMemcpy(stats, c->dev.stats + g, sizeof(*stats), hipMemcpyDeviceToHost));
+    return SPA_OK;
+}
+
+int spa_edit_nodes_device(spa_ctx *c, int count, const spa_node_row *d_rows, const int *d_mask, int *d_status_out,
+                          void *hip_stream)
+{
+    if (!c) return sfail(SPA_EINVAL, "ctx is NULL");
+    if (count < 0) return sfail(SPA_EINVAL, "negative count");
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (c->N > SPA_EDIT_MAX_NODES) return sfail(SPA_ERANGE, "device edits need max_nodes <= SPA_EDIT_MAX_NODES (4096)");
+    if (count == 0) return SPA_OK;
+    if (!d_rows) return sfail(SPA_EINVAL, "d_rows is NULL");
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    int rc = begin_edit(c, s);
+    if (rc != SPA_OK) return rc;
+    hipLaunchKernelGGL(spa_edit_nodes_kernel, dim3((unsigned)count), dim3(GE_THREADS), 0, s, edit_args(c), count, d_rows,
+                       d_mask, d_status_out);
+    return end_edit(c, s);
+}
+
+int spa_edit_constraints_device(spa_ctx *c, int count, const spa_con_row *d_rows, const int *d_mask, int *d_added_out,
+                                int *d_status_out, void *hip_stream)
+{
+    if (!c) return sfail(SPA_EINVAL, "ctx is NULL");
+    if (count < 0) return sfail(SPA_EINVAL, "negative count");
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (c->N > SPA_EDIT_MAX_NODES) return sfail(SPA_ERANGE, "device edits need max_nodes <= SPA_EDIT_MAX_NODES (4096)");
+    if (count == 0) return SPA_OK;
+    if (!d_rows) return sfail(SPA_EINVAL, "d_rows is NULL");
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    int rc = begin_edit(c, s);
+    if (rc != SPA_OK) return rc;
+    hipLaunchKernelGGL(spa_edit_constraints_kernel, dim3((unsigned)count), dim3(GE_THREADS), spa_edit_lds(c->N), s,
+                       edit_args(c), count, d_rows, d_mask, d_added_out, d_status_out);
+    return end_edit(c, s);
+}
+
+int spa_get_edit_info(spa_ctx *c, int *n_refused, int *first_status)
+{
+    if (!c) return sfail(SPA_EINVAL, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(c->mu);
+    int rc = wait_last(c);
+    if (rc != SPA_OK) return rc;
+    unsigned long long info[2] = {0, 0};
+    SCHK(hipMemcpy(info, c->d_edit_info, sizeof(info), hipMemcpyDeviceToHost));
+    if (n_refused) *n_refused = (int)info[0];
+    if (first_status) *first_status = info[0] ? -(int)(info[1] & 0xff) : SPA_OK;
+    const unsigned long long fresh[2] = {0, ~0ull};
+    SCHK(hipMemcpy(c->d_edit_info, fresh, sizeof(fresh), hipMemcpyHostToDevice));
+    c->edit_seq = 0;
+    return SPA_OK;
+}
+
+int spa_download_graph(spa_ctx *c, int g, int *n_nodes, int *n_cons, int *n_pairs, int *ids_out, int *ends_out,
+                       double *means_out, double *precs_out, int *inc_off_out, int *inc_out, int *nbr_off_out,
+                       int *nbr_out, int *pair_off_out, int *pair_con_out)
+{
+    int rc = check_graph(c, g);
+    if (rc != SPA_OK) return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (c->dirty[g] && (rc = upload_graph(c, g)) != SPA_OK) return rc;
+    if ((rc = wait_last(c)) != SPA_OK) return rc;
+    const size_t N = (size_t)c->N, M = (size_t)c->M;
+    SpaHdr h{};
+    SCHK(hipMemcpy(&h, c->d_hdr + g, sizeof(h), hipMemcpyDeviceToHost));
+    if (h.n_nodes < 0 || h.n_nodes > c->N || h.n_cons < 0 || h.n_cons > c->M || h.n_pairs < 0 || h.n_pairs > h.n_cons)
+        return sfail(SPA_EHIP, "the device header of the graph is out of range");
+    if (n_nodes) *n_nodes = h.n_nodes;
+    if (n_cons) *n_cons = h.n_cons;
+    if (n_pairs) *n_pairs = h.n_pairs;
+    const size_t n = (size_t)h.n_nodes, m = (size_t)h.n_cons;
+#define SPA_DOWN(out, src, bytes) \
+    if ((out) && (bytes) > 0) SCHK(hipMemcpy((out), (src), (bytes), hipMemcpyDeviceToHost))
+    SPA_DOWN(ids_out, c->d_ids + g * N, sizeof(int) * n);
+    SPA_DOWN(ends_out, c->d_con_nd + g * M, sizeof(int2) * m);
+    SPA_DOWN(means_out, c->d_con_mean + g * M * 3, sizeof(double) * 3 * m);
+    SPA_DOWN(precs_out, c->d_con_prec + g * M * 9, sizeof(double) * 9 * m);
+    SPA_DOWN(inc_off_out, c->d_inc_off + g * (N + 1), sizeof(int) * (n + 1));
+    SPA_DOWN(inc_out, c->d_inc + g * 2 * M, sizeof(int) * 2 * m);
+    SPA_DOWN(nbr_off_out, c->d_nbr_off + g * (N + 1), sizeof(int) * (n + 1));
+    SPA_DOWN(pair_off_out, c->d_pair_off + g * (M + 1), sizeof(int) * ((size_t)h.n_pairs + 1));
+    SPA_DOWN(pair_con_out, c->d_pair_con + g * M, sizeof(int) * m);
+    if (nbr_out && m > 0) {
+        int total = 0;
+        SCHK(hipMemcpy(&total, c->d_nbr_off + g * (N + 1) + n, sizeof(int), hipMemcpyDeviceToHost));
+        if (total < 0 || (size_t)total > 2 * m) return sfail(SPA_EHIP, "the device neighbour offsets of the graph are out of range");
+        SPA_DOWN(nbr_out, c->d_nbr + g * 2 * M, sizeof(int2) * (size_t)total);
+    }
+#undef SPA_DOWN
     return SPA_OK;
 }
 

@@ -29,6 +29,7 @@
 
 #include "../../include/slam2d/spa.h"
 #include "detmath.h"
+#include "graph_edit_device.h"
 
 namespace s2d {
 
@@ -659,6 +660,350 @@ __global__ __launch_bounds__(SPA_THREADS) void spa_solve_kernel(SpaDev D, int g_
     st.final_cost = cost;
     st.lambda = lambda;
     if (t == 0) D.stats[g] = st;
+}
+
+// =================================================================================================
+// spa_edit_nodes_kernel / spa_edit_constraints_kernel: addNode and addConstraint on the device
+// (graph_edit_device.h: one workgroup per row, the first row of a graph leads it; its wave 0 applies the graph's rows
+// in row order, SpaGraph::find's "last node with the id" as a wave maximum).  New nodes only extend the offset lists.
+// New constraints rebuild the six lists to SpaGraph::compile()'s bits:
+//   inc      a stable bucket fill of the 2m constraint ends by node;
+//   sweep 1  64 nodes at a time, each node's neighbour set as a bit map of max_nodes bits in LDS, set from its
+//            incident list: the popcounts give its neighbour count, its count of neighbours above it (the pairs it
+//            is the lower end of) and its count of constraints to nodes above it; prefix sums over the nodes give
+//            nbr_off, each node's first pair and its first pair_con position ((lo, hi) order);
+//   sweep 2  per incident entry whose other end is above the node: the pair is the node's first pair plus the
+//            popcount rank of the other end among the bits above the node; pair_con's position is the node's first
+//            position plus the entries to lower neighbours above the node plus the earlier entries to the same one,
+//            both counted along the incident list, which is in constraint order; pair_off from each pair's first;
+//   sweep 3  per incident entry: nbr[nbr_off + popcount rank of the other end] = (other end, the constraint's pair).
+// The per-constraint pair and the three per-node counts live in the graph's slice of the solver's scratch, which no
+// compute expects to survive.  LDS: max(max_nodes + 1 ints, 64 rows of ceil(max_nodes / 32) words and as many
+// uint16 word prefixes) + a few hundred ints.
+// =================================================================================================
+constexpr int SPA_EDIT_TILE = 64;
+
+struct SpaEdit {
+    SpaHdr *hdr;
+    double *poses;
+    int *ids;  // [G][max_nodes]
+    int2 *con_nd;
+    double *con_mean, *con_prec;
+    int *inc_off, *inc, *nbr_off;
+    int2 *nbr;
+    int *pair_off, *pair_con;
+    double *scratch;
+    unsigned long long *info;  // ge_refuse
+    int N, M, G;
+    unsigned seq;
+};
+
+__host__ __device__ inline int spa_edit_words(int max_nodes) { return (max_nodes + 31) / 32; }
+__host__ __device__ inline size_t spa_edit_lds(int max_nodes)
+{
+    const size_t tile = (size_t)SPA_EDIT_TILE * spa_edit_words(max_nodes) * 6, fill = sizeof(int) * ((size_t)max_nodes + 1);
+    return ((tile > fill ? tile : fill) + 15) / 16 * 16 + sizeof(int) * (GE_THREADS + GE_WAVES + SPA_EDIT_TILE + 4);
+}
+
+__device__ __forceinline__ int spa_wave_max(int v)
+{
+    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+// bits of row `bm` below bit j
+__device__ __forceinline__ int spa_edit_rank(const unsigned *bm, const unsigned short *pre, int j)
+{
+    return (int)pre[j >> 5] + __popc(bm[j >> 5] & ((1u << (j & 31)) - 1u));
+}
+
+// One sweep over the nodes, SPA_EDIT_TILE at a time: the tile's bit maps (and word prefixes when PREFIX), then
+// per_tile(k0, k1) by all lanes and per_entry(node, row, other end, position in inc) for every incident entry.
+template <bool PREFIX, class PerTile, class PerEntry>
+__device__ inline void spa_edit_sweep(int n, int W, const int *inc_off, const int *inc, const int2 *con_nd, unsigned *bm,
+                                      unsigned short *pre, PerTile per_tile, PerEntry per_entry)
+{
+    const int t = threadIdx.x;
+    for (int k0 = 0; k0 < n; k0 += SPA_EDIT_TILE) {
+        const int k1 = min(k0 + SPA_EDIT_TILE, n);
+        for (int i = t; i < SPA_EDIT_TILE * W; i += GE_THREADS) bm[i] = 0;
+        __syncthreads();
+        const int x0 = inc_off[k0], x1 = inc_off[k1];
+        int k = 0, o = 0;
+        // an entry's node: the last k with inc_off[k] <= x
+        auto locate = [&](int x) {
+            int lo = k0, hi = k1;
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (inc_off[mid] <= x) lo = mid;
+                else hi = mid;
+            }
+            k = lo;
+            const int e = inc[x];
+            const int2 c = con_nd[e >> 1];
+            o = (e & 1) ? c.x : c.y;
+        };
+        for (int x = x0 + t; x < x1; x += GE_THREADS) {
+            locate(x);
+            atomicOr(&bm[(k - k0) * W + (o >> 5)], 1u << (o & 31));
+        }
+        __syncthreads();
+        if (PREFIX) {
+            if (t < k1 - k0) {
+                int run = 0;
+                for (int w = 0; w < W; ++w) {
+                    pre[t * W + w] = (unsigned short)run;
+                    run += __popc(bm[t * W + w]);
+                }
+            }
+            __syncthreads();
+        }
+        per_tile(k0, k1);
+        for (int x = x0 + t; x < x1; x += GE_THREADS) {
+            locate(x);
+            per_entry(k, k - k0, o, x);
+        }
+        __syncthreads();
+    }
+}
+
+// all lanes of the leader: graph g's six lists from its n nodes and m constraints
+__device__ inline void spa_edit_rebuild(const SpaEdit &E, int g, int n, int m, unsigned char *smem)
+{
+    const int t = threadIdx.x;
+    const size_t N = (size_t)E.N, M = (size_t)E.M;
+    const int W = spa_edit_words(E.N);
+    const size_t tile = (size_t)SPA_EDIT_TILE * W * 6, fill = sizeof(int) * (N + 1);
+    int *cur = (int *)smem;
+    unsigned *bm = (unsigned *)smem;
+    unsigned short *pre = (unsigned short *)(smem + (size_t)SPA_EDIT_TILE * W * 4);
+    int *s_b = (int *)(smem + ((tile > fill ? tile : fill) + 15) / 16 * 16), *sw = s_b + GE_THREADS, *s_cnt = sw + GE_WAVES;
+    const int2 *con_nd = E.con_nd + g * M;
+    int *inc_off = E.inc_off + g * (N + 1), *inc = E.inc + g * 2 * M, *nbr_off = E.nbr_off + g * (N + 1);
+    int2 *nbr = E.nbr + g * 2 * M;
+    int *pair_off = E.pair_off + g * (M + 1), *pair_con = E.pair_con + g * M;
+    int *pairidx = (int *)(E.scratch + g * spa_scratch_doubles(E.N, E.M));
+    int *pb = pairidx + M, *cb = pb + (N + 1);
+
+    ge_bucket_fill(
+        n, 2 * m, cur, s_b, sw, inc_off,
+        [&](int x) {
+            const int2 c = con_nd[x >> 1];
+            return (x & 1) ? c.y : c.x;
+        },
+        [&](int x, int pos) { inc[pos] = x; });
+    __threadfence_block();
+    __syncthreads();
+
+    // sweep 1: the counts
+    spa_edit_sweep<false>(
+        n, W, inc_off, inc, con_nd, bm, pre,
+        [&](int k0, int k1) {
+            if (t < k1 - k0) {
+                const int k = k0 + t;
+                int total = 0, above = 0;
+                for (int w = 0; w < W; ++w) {
+                    const unsigned b = bm[t * W + w];
+                    total += __popc(b);
+                    if (w > (k >> 5)) above += __popc(b);
+                    else if (w == (k >> 5)) above += __popc(b & ~((2u << (k & 31)) - 1u));
+                }
+                nbr_off[k] = total;
+                pb[k] = above;
+            }
+        },
+        [&](int, int, int, int) {});
+    // and each node's constraints to nodes above it, counted over the incident entries
+    for (int k0 = 0; k0 < n; k0 += SPA_EDIT_TILE) {
+        const int k1 = min(k0 + SPA_EDIT_TILE, n);
+        if (t < SPA_EDIT_TILE) s_cnt[t] = 0;
+        __syncthreads();
+        for (int x = inc_off[k0] + t; x < inc_off[k1]; x += GE_THREADS) {
+            int lo = k0, hi = k1;
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (inc_off[mid] <= x) lo = mid;
+                else hi = mid;
+            }
+            const int e = inc[x];
+            const int2 c = con_nd[e >> 1];
+            if (((e & 1) ? c.x : c.y) > lo) atomicAdd(&s_cnt[lo - k0], 1);
+        }
+        __syncthreads();
+        if (t < k1 - k0) cb[k0 + t] = s_cnt[t];
+        __syncthreads();
+    }
+    __threadfence_block();
+    __syncthreads();
+    ge_exscan_array(nbr_off, n, sw);
+    const int n_pairs = ge_exscan_array(pb, n, sw);
+    ge_exscan_array(cb, n, sw);
+
+    // sweep 2: pairs and pair_con
+    spa_edit_sweep<true>(
+        n, W, inc_off, inc, con_nd, bm, pre, [&](int, int) {},
+        [&](int k, int row, int o, int x) {
+            if (o <= k) return;
+            const unsigned *b = bm + row * W;
+            const unsigned short *p = pre + row * W;
+            const int pair = pb[k] + spa_edit_rank(b, p, o) - spa_edit_rank(b, p, k + 1);
+            int before = 0, same = 0;
+            for (int y = inc_off[k]; y < inc_off[k + 1]; ++y) {
+                const int e = inc[y];
+                const int2 c = con_nd[e >> 1];
+                const int oo = (e & 1) ? c.x : c.y;
+                before += oo > k && oo < o;
+                same += y < x && oo == o;
+            }
+            const int ci = inc[x] >> 1;
+            pair_con[cb[k] + before + same] = ci;
+            if (same == 0) pair_off[pair] = cb[k] + before;
+            pairidx[ci] = pair;
+        });
+    if (t == 0) pair_off[n_pairs] = m;
+    __threadfence_block();
+    __syncthreads();
+
+    // sweep 3: the neighbour lists
+    spa_edit_sweep<true>(
+        n, W, inc_off, inc, con_nd, bm, pre, [&](int, int) {},
+        [&](int k, int row, int o, int x) {
+            nbr[nbr_off[k] + spa_edit_rank(bm + row * W, pre + row * W, o)] = make_int2(o, pairidx[inc[x] >> 1]);
+        });
+    if (t == 0) {
+        SpaHdr h = E.hdr[g];
+        h.n_nodes = n;
+        h.n_cons = m;
+        h.n_pairs = n_pairs;
+        E.hdr[g] = h;
+    }
+}
+
+// a row that names no graph of the context: true when the workgroup is done with it
+__device__ inline bool spa_edit_bad_row(const SpaEdit &E, int row, int g, int *added_out, int *status_out)
+{
+    if (g >= 0 && g < E.G) return false;
+    if (threadIdx.x == 0) {
+        if (added_out) added_out[row] = 0;
+        if (status_out) status_out[row] = g < 0 ? SPA_OK : SPA_EINVAL;
+        if (g >= 0) ge_refuse(E.info, E.seq, row, SPA_EINVAL);
+    }
+    return true;
+}
+
+__global__ void __launch_bounds__(GE_THREADS)
+spa_edit_nodes_kernel(SpaEdit E, int count, const spa_node_row *__restrict__ rows, const int *__restrict__ mask,
+                      int *__restrict__ status_out)
+{
+    const int row = blockIdx.x, lane = threadIdx.x & 63;
+    const int g = rows[row].graph;
+    if (spa_edit_bad_row(E, row, g, nullptr, status_out)) return;
+    if (!ge_is_leader(rows, sizeof(spa_node_row), row, g)) return;
+    if (threadIdx.x >= 64) return;  // wave 0 alone from here: no workgroup barrier below
+    const size_t N = (size_t)E.N, M = (size_t)E.M;
+    const int n0 = E.hdr[g].n_nodes;
+    int n = n0;
+    for (int base = row; base < count; base += 64) {
+        const int j = base + lane;
+        unsigned long long todo = __ballot(j < count && rows[j].graph == g);
+        while (todo) {
+            const int r = base + __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            int st = SPA_OK;
+            if (!mask || mask[r] == 1) {
+                if (n >= E.N) {
+                    st = SPA_ERANGE;
+                } else {
+                    if (lane == 0) E.ids[g * N + n] = rows[r].id;
+                    if (lane < 3) E.poses[(g * N + n) * 3 + lane] = rows[r].pose[lane];
+                    ++n;
+                }
+            }
+            if (lane == 0) {
+                if (status_out) status_out[r] = st;
+                if (st != SPA_OK) ge_refuse(E.info, E.seq, r, st);
+            }
+        }
+    }
+    if (n == n0) return;
+    // the new nodes have no constraint: their lists are empty
+    int *inc_off = E.inc_off + g * (N + 1), *nbr_off = E.nbr_off + g * (N + 1);
+    const int ie = n0 > 0 ? inc_off[n0] : 0, ne = n0 > 0 ? nbr_off[n0] : 0;
+    for (int k = (n0 > 0 ? n0 + 1 : 0) + lane; k <= n; k += 64) {
+        inc_off[k] = ie;
+        nbr_off[k] = ne;
+    }
+    if (lane == 0) {
+        if (n0 == 0) E.pair_off[g * (M + 1)] = 0;
+        E.hdr[g].n_nodes = n;
+    }
+}
+
+__global__ void __launch_bounds__(GE_THREADS)
+spa_edit_constraints_kernel(SpaEdit E, int count, const spa_con_row *__restrict__ rows, const int *__restrict__ mask,
+                            int *__restrict__ added_out, int *__restrict__ status_out)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char spa_edit_smem[];
+    __shared__ int s_m;
+    const int row = blockIdx.x, lane = threadIdx.x & 63;
+    const int g = rows[row].graph;
+    if (spa_edit_bad_row(E, row, g, added_out, status_out)) return;
+    if (!ge_is_leader(rows, sizeof(spa_con_row), row, g)) return;
+    const size_t N = (size_t)E.N, M = (size_t)E.M;
+    const SpaHdr h = E.hdr[g];
+    const int n = h.n_nodes, m0 = h.n_cons;
+    if (threadIdx.x < 64) {
+        const int *ids = E.ids + g * N;
+        int m = m0;
+        for (int base = row; base < count; base += 64) {
+            const int j = base + lane;
+            unsigned long long todo = __ballot(j < count && rows[j].graph == g);
+            while (todo) {
+                const int r = base + __ffsll((long long)todo) - 1;
+                todo &= todo - 1;
+                int st = SPA_OK, added = 0;
+                if (!mask || mask[r] == 1) {
+                    const int id0 = rows[r].id0, id1 = rows[r].id1;
+                    if (id0 == id1) {
+                        st = SPA_EINVAL;
+                    } else {
+                        int ni0 = -1, ni1 = -1;  // the LAST node with the id
+                        for (int k = lane; k < n; k += 64) {
+                            const int id = ids[k];
+                            if (id == id0) ni0 = k;
+                            if (id == id1) ni1 = k;
+                        }
+                        ni0 = spa_wave_max(ni0);
+                        ni1 = spa_wave_max(ni1);
+                        if (ni0 >= 0 && ni1 >= 0) {
+                            if (ni0 == ni1) {
+                                st = SPA_EINVAL;
+                            } else if (m >= E.M) {
+                                st = SPA_ERANGE;
+                            } else {
+                                if (lane == 0) E.con_nd[g * M + m] = make_int2(ni0, ni1);
+                                if (lane < 3) E.con_mean[(g * M + m) * 3 + lane] = rows[r].mean[lane];
+                                if (lane < 9) E.con_prec[(g * M + m) * 9 + lane] = rows[r].prec[lane];
+                                ++m;
+                                added = 1;
+                            }
+                        }
+                    }
+                }
+                if (lane == 0) {
+                    if (added_out) added_out[r] = added;
+                    if (status_out) status_out[r] = st;
+                    if (st != SPA_OK) ge_refuse(E.info, E.seq, r, st);
+                }
+            }
+        }
+        if (lane == 0) s_m = m;
+    }
+    __threadfence_block();
+    __syncthreads();
+    const int m = s_m;
+    if (m == m0) return;
+    spa_edit_rebuild(E, g, n, m, spa_edit_smem);
 }
 
 }  // namespace s2d

@@ -43,6 +43,11 @@ NEAR_CHAIN_DTYPE = np.dtype([(k, np.int32) for k in ("begin", "length", "closest
 CLOSEST_ITEM_DTYPE = np.dtype([(k, np.int32) for k in ("graph", "scan", "begin", "length")])
 CLOSEST_DTYPE = np.dtype([(k, np.int32) for k in ("closest", "linked")])
 SOURCE_DTYPE = np.dtype([(k, np.int32) for k in ("slot", "chain")])
+EDGE_ROW_DTYPE = np.dtype([(k, np.int32) for k in ("graph", "source", "target", "pad_")])
+
+
+class KlEdgeRow(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("graph", "source", "target", "pad_")]
 
 
 def _declare(L):
@@ -76,6 +81,10 @@ def _declare(L):
     L.kl_closest_device.argtypes = [vp, i, vp, vp, vp]
     L.kl_emit_batch_device.argtypes = [vp, i, i, i, vp, vp, vp, vp, vp, vp]
     L.kl_get_emit_info.argtypes = [vp, P(i), P(i)]
+    L.kl_edit_vertices_device.argtypes = [vp, i, vp, vp, vp, vp, vp]
+    L.kl_edit_edges_device.argtypes = [vp, i, vp, vp, vp, vp]
+    L.kl_get_edit_info.argtypes = [vp, P(i), P(i)]
+    L.kl_download_graph.argtypes = [vp, i, P(i), P(i), vp, vp, vp]
     L.kl_set_timing.argtypes = [vp, i]
     L.kl_num_kernels.restype = i
     L.kl_kernel_name.restype = C.c_char_p
@@ -249,6 +258,34 @@ class LoopSearchFleet:
         total, status = C.c_int(0), C.c_int(0)
         self._check(self.L.kl_get_emit_info(self.h, C.byref(total), C.byref(status)), "kl_get_emit_info")
         return total.value, status.value
+
+    # ------------------------------------------------------------------------------------------------ device edits
+    def edit_vertices_device(self, count: int, d_graph: int, d_expect_id: int = 0, d_id: int = 0, d_status: int = 0,
+                             hip_stream: int = 0):
+        """kl_edit_vertices_device: row i adds a vertex to graph d_graph[i] (device int array)."""
+        self._check(self.L.kl_edit_vertices_device(self.h, int(count), _dp(d_graph), _dp(d_expect_id), _dp(d_id),
+                                                   _dp(d_status), _dp(hip_stream)), "kl_edit_vertices_device")
+
+    def edit_edges_device(self, count: int, d_rows: int, d_is_new: int = 0, d_status: int = 0, hip_stream: int = 0):
+        """kl_edit_edges_device: `count` kl_edge_row rows (EDGE_ROW_DTYPE) at device address d_rows."""
+        self._check(self.L.kl_edit_edges_device(self.h, int(count), _dp(d_rows), _dp(d_is_new), _dp(d_status),
+                                                _dp(hip_stream)), "kl_edit_edges_device")
+
+    def edit_info(self):
+        """(rows refused since the last call, status of the first); waits."""
+        n, st = C.c_int(0), C.c_int(0)
+        self._check(self.L.kl_get_edit_info(self.h, C.byref(n), C.byref(st)), "kl_get_edit_info")
+        return n.value, st.value
+
+    def download_graph(self, g: int) -> dict:
+        """Graph g's DEVICE arrays (pending host edits are uploaded first): n_scans, n_edges, ends [m, 2], adj_off
+        [n + 1], adj [2m, 2] = other end, edge index."""
+        n, m = C.c_int(0), C.c_int(0)
+        self._check(self.L.kl_download_graph(self.h, g, C.byref(n), C.byref(m), None, None, None), "kl_download_graph")
+        n, m = n.value, m.value
+        ends, off, adj = np.zeros((m, 2), np.int32), np.zeros(n + 1, np.int32), np.zeros((2 * m, 2), np.int32)
+        self._check(self.L.kl_download_graph(self.h, g, None, None, _hp(ends), _hp(off), _hp(adj)), "kl_download_graph")
+        return {"n_scans": n, "n_edges": m, "ends": ends, "adj_off": off, "adj": adj}
 
     # ------------------------------------------------------------------------------------------------ timing
     def set_timing(self, enable: bool):

@@ -23,6 +23,21 @@ SPA_NOT_RUN, SPA_NO_FIXED, SPA_DISCONNECTED, SPA_NOT_POSDEF, SPA_FACTOR_RANGE = 
 SPA_SOLVER_PCG, SPA_SOLVER_CHOLESKY = 0, 1
 SOLVERS = {"pcg": SPA_SOLVER_PCG, "cholesky": SPA_SOLVER_CHOLESKY}
 SPA_FIXED_FROM_PARAMS = -2147483648
+SPA_EDIT_MAX_NODES = 4096
+
+
+class SpaNodeRow(C.Structure):
+    _fields_ = [("graph", C.c_int), ("id", C.c_int), ("pose", C.c_double * 3)]
+
+
+class SpaConRow(C.Structure):
+    _fields_ = [("graph", C.c_int), ("id0", C.c_int), ("id1", C.c_int), ("pad_", C.c_int), ("mean", C.c_double * 3),
+                ("prec", C.c_double * 9)]
+
+
+NODE_ROW_DTYPE = np.dtype([("graph", np.int32), ("id", np.int32), ("pose", np.float64, 3)])
+CON_ROW_DTYPE = np.dtype([("graph", np.int32), ("id0", np.int32), ("id1", np.int32), ("pad_", np.int32),
+                          ("mean", np.float64, 3), ("prec", np.float64, 9)])
 
 
 class SpaParams(C.Structure):
@@ -65,6 +80,10 @@ def _declare(L):
     L.spa_device_poses.argtypes = [vp, i, P(vp), P(i)]
     L.spa_get_stats.argtypes = [vp, i, P(SpaStats)]
     L.spa_poison_scratch.argtypes = [vp, i]
+    L.spa_edit_nodes_device.argtypes = [vp, i, vp, vp, vp, vp]
+    L.spa_edit_constraints_device.argtypes = [vp, i, vp, vp, vp, vp, vp]
+    L.spa_get_edit_info.argtypes = [vp, P(i), P(i)]
+    L.spa_download_graph.argtypes = [vp, i, P(i), P(i), P(i)] + [vp] * 10
     L._spa_declared = True
 
 
@@ -285,6 +304,43 @@ class SpaFleet:
 
     def poison_scratch(self, byte: int = 0xFF):
         self._check(self.L.spa_poison_scratch(self.h, int(byte)), "spa_poison_scratch")
+
+    # ------------------------------------------------------------------------------------------------ device edits
+    def edit_nodes_device(self, count: int, d_rows: int, d_mask: int = 0, d_status: int = 0, hip_stream: int = 0):
+        """spa_edit_nodes_device: `count` spa_node_row rows (NODE_ROW_DTYPE) at device address d_rows."""
+        v = lambda a: C.c_void_p(int(a) or None)  # noqa: E731
+        self._check(self.L.spa_edit_nodes_device(self.h, int(count), v(d_rows), v(d_mask), v(d_status), v(hip_stream)),
+                    "spa_edit_nodes_device")
+
+    def edit_constraints_device(self, count: int, d_rows: int, d_mask: int = 0, d_added: int = 0, d_status: int = 0,
+                                hip_stream: int = 0):
+        """spa_edit_constraints_device: `count` spa_con_row rows (CON_ROW_DTYPE) at device address d_rows."""
+        v = lambda a: C.c_void_p(int(a) or None)  # noqa: E731
+        self._check(self.L.spa_edit_constraints_device(self.h, int(count), v(d_rows), v(d_mask), v(d_added), v(d_status),
+                                                       v(hip_stream)), "spa_edit_constraints_device")
+
+    def edit_info(self):
+        """(rows refused since the last call, status of the first); waits."""
+        n, st = C.c_int(0), C.c_int(0)
+        self._check(self.L.spa_get_edit_info(self.h, C.byref(n), C.byref(st)), "spa_get_edit_info")
+        return n.value, st.value
+
+    def download_graph(self, g: int) -> dict:
+        """Graph g's DEVICE arrays (pending host edits are uploaded first): ids, ends, means, precs and the six
+        index lists, each cut to its length."""
+        n, m, p = C.c_int(0), C.c_int(0), C.c_int(0)
+        nul = [None] * 10
+        self._check(self.L.spa_download_graph(self.h, g, C.byref(n), C.byref(m), C.byref(p), *nul), "spa_download_graph")
+        n, m, p = n.value, m.value, p.value
+        out = {"ids": np.zeros(n, np.int32), "ends": np.zeros((m, 2), np.int32), "means": np.zeros((m, 3)),
+               "precs": np.zeros((m, 9)), "inc_off": np.zeros(n + 1, np.int32), "inc": np.zeros(2 * m, np.int32),
+               "nbr_off": np.zeros(n + 1, np.int32), "nbr": np.zeros((2 * m, 2), np.int32),
+               "pair_off": np.zeros(p + 1, np.int32), "pair_con": np.zeros(m, np.int32)}
+        self._check(self.L.spa_download_graph(self.h, g, None, None, None, *[_hp(a) for a in out.values()]),
+                    "spa_download_graph")
+        out["nbr"] = out["nbr"][:int(out["nbr_off"][n])].copy()
+        out.update(n_nodes=n, n_cons=m, n_pairs=p)
+        return out
 
 
 class SpaSolver:

@@ -17,6 +17,8 @@
  *   kl_closest_device      GetClosestScanToPose / LinkChainToScan's test for the running scans (Mapper.cpp:962)
  *                          and for a loop chain after SetSensorPose(bestPose) (Mapper.cpp:1032-1035)
  *   kl_emit_batch_device   the candidate chains as the arrays kt_match_batch_device (karto.h) takes
+ *   kl_edit_vertices_device / kl_edit_edges_device   AddVertex / AddEdge again, applied by kernels to rows of
+ *                          device memory ("GRAPH EDITS ON THE DEVICE" below; karto_edit.h feeds them)
  *
  * ONE sensor only: the node has one laser, so a graph's scans are one sensor's and a scan's state id is its index.
  *
@@ -202,6 +204,41 @@ int kl_emit_batch_device(kl_ctx *ctx, int count, int which, int capacity, int *d
                          int *d_base_index_out, kl_source *d_source_out, int *d_n_matches, void *hip_stream);
 /* The last emit's match count before the capacity cut, and its status (waits for it). */
 int kl_get_emit_info(kl_ctx *ctx, int *total_matches, int *status);
+
+/* GRAPH EDITS ON THE DEVICE.  The same edits as kl_add_vertex / kl_add_edge, applied by kernels, stream-ordered,
+ * with no host synchronisation and no copy -- unless a graph has pending HOST edits, which are uploaded first (the
+ * only case in which these calls wait).  They leave the context's device arrays (header, edge list, adjacency) as
+ * host edits followed by the upload would have.  All row arrays are device memory; any output array may be NULL.
+ * One workgroup per row; the first row that names a graph leads it and applies all its rows in row order, so rows
+ * of several graphs may be interleaved.  The cost grows with count and with the touched graphs' sizes.
+ *
+ * A device edit leaves the host's copy of the graphs behind.  kl_add_vertex, kl_add_edge and kl_get_counts then
+ * first pull their graph back (they wait and copy its header and edge list); kl_set_graph and kl_clear_graph
+ * overwrite it.
+ *
+ * kl_edit_vertices_device: row i adds one vertex to graph d_graph[i] (negative: the row is skipped, status KL_OK,
+ * id -1).  d_id_out[i] is the scan count before the row, or -1 when it is refused: with d_expect_id non-NULL and
+ * d_expect_id[i] >= 0, KL_EINVAL unless that count equals it; KL_ERANGE when the graph holds max_scans scans;
+ * KL_EINVAL for a graph >= max_graphs.
+ *
+ * kl_edit_edges_device: AddEdge's rule exactly as kl_add_edge states it, earlier rows of the same call included.
+ * d_is_new_out[i] is 1 or 0 (0 for skipped and refused rows).  Refusals are kl_add_edge's: an end that is not a
+ * vertex, or a self edge, KL_EINVAL; max_edges reached, KL_ERANGE.  A refused row changes nothing and the LATER
+ * ROWS, OF THAT GRAPH TOO, ARE STILL APPLIED: the host ke_commit ends at its first failure, this path does not. */
+typedef struct kl_edge_row {
+    int graph, source, target, pad_;
+} kl_edge_row;
+
+int kl_edit_vertices_device(kl_ctx *ctx, int count, const int *d_graph, const int *d_expect_id, int *d_id_out,
+                            int *d_status_out, void *hip_stream);
+int kl_edit_edges_device(kl_ctx *ctx, int count, const kl_edge_row *d_rows, int *d_is_new_out, int *d_status_out,
+                         void *hip_stream);
+/* Rows the device edits refused since the last call of this function, and the status of the first of them in
+ * (call, row) order (KL_OK: none).  Waits. */
+int kl_get_edit_info(kl_ctx *ctx, int *n_refused, int *first_status);
+/* Inspection: uploads pending host edits, waits, and copies graph g's DEVICE arrays back: ends int[n_edges][2],
+ * adj_off int[n_scans + 1], adj int[2 n_edges][2] (other end, edge index).  Any output may be NULL. */
+int kl_download_graph(kl_ctx *ctx, int g, int *n_scans, int *n_edges, int *ends_out, int *adj_off_out, int *adj_out);
 
 int kl_set_timing(kl_ctx *ctx, int enable);
 /* Accumulated device time per kernel: names kl_kernel_name(i), i < kl_num_kernels(). */

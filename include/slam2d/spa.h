@@ -165,9 +165,60 @@ int spa_compute_device(spa_ctx *ctx, int g_first, int count, const spa_params *p
 /* ids_out int[n], poses_out double[n][3] in node order; either may be NULL.  Waits for the last compute. */
 int spa_get_nodes(spa_ctx *ctx, int g, int *ids_out, double *poses_out);
 /* The same poses on the device, double[n][3]: the d_poses layout kg_build_device and kt_set_scans_device
- * take.  Valid after the compute's stream work, until the graph is edited or the context destroyed. */
+ * take.  The POINTER is fixed for the context's life (graph g owns rows [g * max_nodes, (g + 1) * max_nodes) of
+ * one array), so it may be fetched once; the contents are valid after the compute's stream work.  *n is the
+ * graph's node count, for which the call pulls a graph edited on the device back (it then waits). */
 int spa_device_poses(spa_ctx *ctx, int g, const double **d_poses, int *n);
 int spa_get_stats(spa_ctx *ctx, int g, spa_stats *stats);
+
+/* GRAPH EDITS ON THE DEVICE.  The same edits as spa_add_node / spa_add_constraint, applied by kernels,
+ * stream-ordered, with no host synchronisation and no copy -- unless a graph has pending HOST edits, which are
+ * uploaded first (the only case in which these calls wait; every graph of a fresh context counts as edited once).
+ * They leave the context's device arrays (header, ids, constraints and the six index lists) as host edits followed
+ * by the upload would have.  Row arrays are device memory; d_mask and the output arrays may be NULL.  One workgroup
+ * per row; the first row that names a graph leads it and applies all its rows in row order, so rows of several
+ * graphs may be interleaved.  A negative graph skips the row; with d_mask a row is applied only where
+ * d_mask[i] == 1 (else status SPA_OK, added 0).  A refused row changes nothing; later rows are still applied.
+ *
+ * Limits: device edits need max_nodes <= SPA_EDIT_MAX_NODES (a node's neighbour set is kept as a bit map in
+ * LDS); a larger context is refused at the call with SPA_ERANGE.  The constraints have no cap of their own: no
+ * list of them is kept in LDS.
+ *
+ * A device edit leaves the host's copy of the graphs behind.  spa_add_node, spa_add_constraint, spa_get_counts,
+ * spa_get_nodes, spa_envelope_blocks, spa_set_n_fixed and spa_device_poses then first pull their graph back (they
+ * wait and copy its header, ids, poses and constraints); spa_set_graph and spa_clear_graph overwrite it.
+ *
+ * spa_edit_nodes_device: appends node (id, pose) and writes the pose into the device poses; the other nodes'
+ * optimised poses persist.  A full graph refuses the row with SPA_ERANGE.
+ * spa_edit_constraints_device: spa_add_constraint's semantics: an unknown id gives added 0 and SPA_OK; id0 == id1,
+ * or both ids resolving to one node, SPA_EINVAL; max_constraints reached, SPA_ERANGE. */
+#define SPA_EDIT_MAX_NODES 4096
+
+typedef struct spa_node_row {
+    int graph, id;
+    double pose[3];
+} spa_node_row;
+
+typedef struct spa_con_row {
+    int graph, id0, id1, pad_;
+    double mean[3];
+    double prec[9];
+} spa_con_row;
+
+int spa_edit_nodes_device(spa_ctx *ctx, int count, const spa_node_row *d_rows, const int *d_mask, int *d_status_out,
+                          void *hip_stream);
+int spa_edit_constraints_device(spa_ctx *ctx, int count, const spa_con_row *d_rows, const int *d_mask,
+                                int *d_added_out, int *d_status_out, void *hip_stream);
+/* Rows the device edits refused since the last call of this function, and the status of the first of them in
+ * (call, row) order (SPA_OK: none).  Waits. */
+int spa_get_edit_info(spa_ctx *ctx, int *n_refused, int *first_status);
+/* Inspection: uploads graph g's pending host edits, waits, and copies its DEVICE arrays back: ids int[n_nodes],
+ * ends int[n_cons][2], means double[n_cons][3], precs double[n_cons][9], inc_off int[n_nodes + 1], inc int[2
+ * n_cons], nbr_off int[n_nodes + 1], nbr int[nbr_off[n_nodes]][2], pair_off int[n_pairs + 1], pair_con
+ * int[n_cons].  Any output may be NULL. */
+int spa_download_graph(spa_ctx *ctx, int g, int *n_nodes, int *n_cons, int *n_pairs, int *ids_out, int *ends_out,
+                       double *means_out, double *precs_out, int *inc_off_out, int *inc_out, int *nbr_off_out,
+                       int *nbr_out, int *pair_off_out, int *pair_con_out);
 
 /* Test hook: fills the working arrays of every graph (not the poses or the graph itself) with byte. */
 int spa_poison_scratch(spa_ctx *ctx, int byte);
