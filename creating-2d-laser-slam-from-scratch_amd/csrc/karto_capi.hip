@@ -8,29 +8,14 @@
 #include <string>
 #include <vector>
 
-#include "host_timing.h"
+#include "stage_runtime.h"
 #include "karto_kernels.hip"
 
 using namespace s2d;
 
 namespace {
-thread_local std::string kt_err;
-
-int kfail(int code, const char *what, hipError_t e = hipSuccess)
-{
-    kt_err = what;
-    if (e != hipSuccess) {
-        kt_err += ": ";
-        kt_err += hipGetErrorString(e);
-    }
-    return code;
-}
-
-#define KCHK(expr)                                              \
-    do {                                                        \
-        hipError_t _e = (expr);                                 \
-        if (_e != hipSuccess) return kfail(KT_EHIP, #expr, _e); \
-    } while (0)
+thread_local StageError kt_err;
+S2D_ASSERT_STATUS_CODES(KT);
 
 enum { K_PREPARE, K_BEGIN, K_BUILD, K_COARSE, K_SELECT, K_FINE, K_CLEAR, K_NUM };
 const char *const k_names[K_NUM] = {"kt_prepare_kernel", "kt_begin_kernel", "kt_build_kernel", "kt_coarse_kernel",
@@ -61,6 +46,7 @@ struct kt_ctx {
     int *d_query = nullptr, *d_bbeg = nullptr, *d_bidx = nullptr;
     kt_result *d_res = nullptr;
     hipStream_t stream = nullptr;
+    DeviceBuffers mem;
     KernelTimer timer;
 
     KtPool pool() const { return KtPool{d_ranges, d_poses, d_npts, d_pts, d_loc, d_bad, d_evt}; }
@@ -68,7 +54,7 @@ struct kt_ctx {
 
 namespace {
 
-#define KT_LAUNCH(which, ...) S2D_TIMED_LAUNCH(c->timer, kfail, KT_EHIP, s, which, __VA_ARGS__)
+#define KT_LAUNCH(which, ...) S2D_TIMED_LAUNCH(c->timer, kt_err.fail, KT_EHIP, s, which, __VA_ARGS__)
 
 int kt_prepare(kt_ctx *c, int first, int count, hipStream_t s)
 {
@@ -106,7 +92,7 @@ int kt_chunk_coarse(kt_ctx *c, int count, int pass, int penalize, int shard, int
 {
     const KtGeom &g = c->g;
     const KtCoarsePlan plan = kt_plan_coarse(c->opt, g, count, pass);
-    if (plan.refused) return kfail(KT_EINVAL, plan.refused);
+    if (plan.refused) return kt_err.fail(KT_EINVAL, plan.refused);
     KT_LAUNCH(K_COARSE, kt_coarse_kernel, dim3((unsigned)plan.blocks), dim3(KT_THREADS), (size_t)g.n * sizeof(int), s,
               g, c->pool(), c->d_state, c->d_grids, c->d_resp, c->d_posmax, count, pass, penalize, shard, nshards,
               plan.angle_group);
@@ -203,10 +189,7 @@ int kt_destroy(kt_ctx *c)
 {
     if (!c) return KT_OK;
     if (c->stream) hipStreamSynchronize(c->stream);
-    void *bufs[] = {c->d_ranges, c->d_poses, c->d_npts,    c->d_pts,     c->d_loc,   c->d_bad,  c->d_evt,
-                    c->d_grids,  c->d_kernel, c->d_state, c->d_resp,    c->d_posmax, c->d_tie_idx, c->d_tie_val,
-                    c->d_query,  c->d_bbeg,  c->d_bidx,    c->d_res, c->d_scratch, c->d_dirty, c->d_dirty_cnt};
-    for (void *b : bufs) hipFree(b);
+    c->mem.free_all();
     c->timer.destroy();
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
@@ -216,23 +199,22 @@ int kt_destroy(kt_ctx *c)
 int kt_create(kt_ctx **out, const kt_laser *laser, const kt_params *params, int max_matches, int max_scans,
               int max_base_per_match)
 {
-    if (!out) return kfail(KT_EINVAL, "out is NULL");
+    if (!out) return kt_err.fail(KT_EINVAL, "out is NULL");
     *out = nullptr;
-    if (!laser) return kfail(KT_EINVAL, "laser is NULL");
+    if (!laser) return kt_err.fail(KT_EINVAL, "laser is NULL");
     if (max_matches < 1 || max_matches > 65535 || max_scans < 1 || max_base_per_match < 0)
-        return kfail(KT_EINVAL, "need 1 <= max_matches <= 65535, max_scans >= 1, max_base_per_match >= 0");
+        return kt_err.fail(KT_EINVAL, "need 1 <= max_matches <= 65535, max_scans >= 1, max_base_per_match >= 0");
     kt_params p;
     if (params) p = *params;
     else kt_default_params(&p);
     KtOptions opt;
     const char *refused = kt_parse_options(opt, [](const char *knob) -> const char * { return getenv(knob); });
-    if (refused) return kfail(KT_EINVAL, refused);
+    if (refused) return kt_err.fail(KT_EINVAL, refused);
     KtGeom g;
     std::vector<unsigned char> kernel;
     const int rc = kt_geometry(*laser, p, opt, g, kernel, refused);
-    if (rc != KT_OK) return kfail(rc, refused);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return kfail(KT_ENODEV, "no HIP device");
+    if (rc != KT_OK) return kt_err.fail(rc, refused);
+    if (!device_present()) return kt_err.fail(KT_ENODEV, "no HIP device");
     kt_ctx *c = new kt_ctx;
     c->laser = *laser;
     c->params = p;
@@ -247,45 +229,43 @@ int kt_create(kt_ctx **out, const kt_laser *laser, const kt_params *params, int 
     hipError_t e;
     if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamDefault)) != hipSuccess) {
         delete c;
-        return kfail(KT_EHIP, "hipStreamCreate", e);
+        return kt_err.fail(KT_EHIP, "hipStreamCreate", e);
     }
     const size_t S = (size_t)max_scans, n = (size_t)g.n, M = (size_t)c->slots;
     const size_t mp = (size_t)g.max_poses, npos = (size_t)g.nxy * g.nxy;
-#define KALLOC(ptr, bytes)                                                                  \
-    if ((e = hipMalloc((void **)&(ptr), (bytes))) != hipSuccess ||                          \
-        (opt.poison && (e = hipMemsetAsync((ptr), 0xA5, (bytes), c->stream)) != hipSuccess)) {  \
-        kt_destroy(c);                                                                      \
-        return kfail(KT_ENOMEM, "hipMalloc " #ptr, e);                                      \
-    }
-    KALLOC(c->d_ranges, sizeof(double) * S * n);
-    KALLOC(c->d_poses, sizeof(double) * S * 3);
-    KALLOC(c->d_npts, sizeof(int) * S);
-    KALLOC(c->d_pts, sizeof(double2) * S * n);
-    KALLOC(c->d_loc, sizeof(double2) * S * n);
-    KALLOC(c->d_bad, S * n);
-    KALLOC(c->d_evt, sizeof(int2) * S * n);
-    KALLOC(c->d_grids, g.grid_stride * M);
-    KALLOC(c->d_kernel, kernel.size());
-    KALLOC(c->d_state, sizeof(KtState) * M);
-    KALLOC(c->d_resp, sizeof(double) * mp * M);
-    KALLOC(c->d_posmax, sizeof(unsigned long long) * npos * M);
-    KALLOC(c->d_tie_idx, sizeof(int) * mp * M);
-    KALLOC(c->d_tie_val, sizeof(double4) * std::max(mp, npos) * M);
-    KALLOC(c->d_query, sizeof(int));
-    KALLOC(c->d_bbeg, sizeof(int) * 2);
-    KALLOC(c->d_bidx, sizeof(int) * std::max<size_t>(1, (size_t)max_base_per_match));
-    KALLOC(c->d_res, sizeof(kt_result));
+    DeviceBuffers &m = c->mem;
+    m.alloc(c->d_ranges, sizeof(double) * S * n);
+    m.alloc(c->d_poses, sizeof(double) * S * 3);
+    m.alloc(c->d_npts, sizeof(int) * S);
+    m.alloc(c->d_pts, sizeof(double2) * S * n);
+    m.alloc(c->d_loc, sizeof(double2) * S * n);
+    m.alloc(c->d_bad, S * n);
+    m.alloc(c->d_evt, sizeof(int2) * S * n);
+    m.alloc(c->d_grids, g.grid_stride * M);
+    m.alloc(c->d_kernel, kernel.size());
+    m.alloc(c->d_state, sizeof(KtState) * M);
+    m.alloc(c->d_resp, sizeof(double) * mp * M);
+    m.alloc(c->d_posmax, sizeof(unsigned long long) * npos * M);
+    m.alloc(c->d_tie_idx, sizeof(int) * mp * M);
+    m.alloc(c->d_tie_val, sizeof(double4) * std::max(mp, npos) * M);
+    m.alloc(c->d_query, sizeof(int));
+    m.alloc(c->d_bbeg, sizeof(int) * 2);
+    m.alloc(c->d_bidx, sizeof(int) * std::max<size_t>(1, (size_t)max_base_per_match));
+    m.alloc(c->d_res, sizeof(kt_result));
     if (kt_binned_eligible(opt, g, max_base_per_match)) {
-        KALLOC(c->d_scratch, sizeof(int) * M * std::max<size_t>(1, (size_t)max_base_per_match) * n);
-        KALLOC(c->d_dirty, sizeof(int) * M * (size_t)g.ntiles);
-        KALLOC(c->d_dirty_cnt, sizeof(int) * M);
+        m.alloc(c->d_scratch, sizeof(int) * M * std::max<size_t>(1, (size_t)max_base_per_match) * n);
+        m.alloc(c->d_dirty, sizeof(int) * M * (size_t)g.ntiles);
+        m.alloc(c->d_dirty_cnt, sizeof(int) * M);
     }
-#undef KALLOC
+    if ((e = m.error) != hipSuccess || (opt.poison && (e = m.fill(0xA5, c->stream)) != hipSuccess)) {
+        kt_destroy(c);
+        return kt_err.fail(KT_ENOMEM, "hipMalloc", e);
+    }
     if (plan.prepare_attr &&
         (e = hipFuncSetAttribute((const void *)kt_prepare_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)plan.prepare_lds)) != hipSuccess) {
         kt_destroy(c);
-        return kfail(KT_EHIP, "hipFuncSetAttribute(kt_prepare_kernel)", e);
+        return kt_err.fail(KT_EHIP, "hipFuncSetAttribute(kt_prepare_kernel)", e);
     }
     if ((e = hipMemsetAsync(c->d_grids, 0, g.grid_stride * M, c->stream)) != hipSuccess ||
         (e = hipMemsetAsync(c->d_npts, 0, sizeof(int) * S, c->stream)) != hipSuccess ||
@@ -293,7 +273,7 @@ int kt_create(kt_ctx **out, const kt_laser *laser, const kt_params *params, int 
             hipSuccess ||
         (e = hipStreamSynchronize(c->stream)) != hipSuccess) {
         kt_destroy(c);
-        return kfail(KT_EHIP, "initialising the context", e);
+        return kt_err.fail(KT_EHIP, "initialising the context", e);
     }
     *out = c;
     return KT_OK;
@@ -301,7 +281,7 @@ int kt_create(kt_ctx **out, const kt_laser *laser, const kt_params *params, int 
 
 int kt_get_grid_info(kt_ctx *c, int *out)
 {
-    if (!c || !out) return kfail(KT_EINVAL, "NULL argument");
+    if (!c || !out) return kt_err.fail(KT_EINVAL, "NULL argument");
     kt_grid_info_words(c->g, out);
     return KT_OK;
 }
@@ -309,39 +289,39 @@ int kt_get_grid_info(kt_ctx *c, int *out)
 int kt_set_scans_device(kt_ctx *c, int first, int count, const double *d_ranges, const double *d_poses,
                         void *hip_stream)
 {
-    if (!c || !d_ranges || !d_poses) return kfail(KT_EINVAL, "NULL argument");
-    if (first < 0 || count < 0 || first + count > c->max_scans) return kfail(KT_EINVAL, "scan slots out of range");
+    if (!c || !d_ranges || !d_poses) return kt_err.fail(KT_EINVAL, "NULL argument");
+    if (first < 0 || count < 0 || first + count > c->max_scans) return kt_err.fail(KT_EINVAL, "scan slots out of range");
     if (count == 0) return KT_OK;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
     const size_t n = (size_t)c->g.n;
     if (d_ranges != c->d_ranges + (size_t)first * n)
-        KCHK(hipMemcpyAsync(c->d_ranges + (size_t)first * n, d_ranges, sizeof(double) * n * count,
+        S2D_CHK(kt_err, KT_EHIP, hipMemcpyAsync(c->d_ranges + (size_t)first * n, d_ranges, sizeof(double) * n * count,
                             hipMemcpyDeviceToDevice, s));
     if (d_poses != c->d_poses + (size_t)first * 3)
-        KCHK(hipMemcpyAsync(c->d_poses + (size_t)first * 3, d_poses, sizeof(double) * 3 * count,
+        S2D_CHK(kt_err, KT_EHIP, hipMemcpyAsync(c->d_poses + (size_t)first * 3, d_poses, sizeof(double) * 3 * count,
                             hipMemcpyDeviceToDevice, s));
     return kt_prepare(c, first, count, s);
 }
 
 int kt_set_scans(kt_ctx *c, int first, int count, const double *ranges, const double *poses)
 {
-    if (!c || !ranges || !poses) return kfail(KT_EINVAL, "NULL argument");
-    if (first < 0 || count < 0 || first + count > c->max_scans) return kfail(KT_EINVAL, "scan slots out of range");
+    if (!c || !ranges || !poses) return kt_err.fail(KT_EINVAL, "NULL argument");
+    if (first < 0 || count < 0 || first + count > c->max_scans) return kt_err.fail(KT_EINVAL, "scan slots out of range");
     if (count == 0) return KT_OK;
     const size_t n = (size_t)c->g.n;
-    KCHK(hipMemcpyAsync(c->d_ranges + (size_t)first * n, ranges, sizeof(double) * n * count, hipMemcpyHostToDevice,
+    S2D_CHK(kt_err, KT_EHIP, hipMemcpyAsync(c->d_ranges + (size_t)first * n, ranges, sizeof(double) * n * count, hipMemcpyHostToDevice,
                         c->stream));
-    KCHK(hipMemcpyAsync(c->d_poses + (size_t)first * 3, poses, sizeof(double) * 3 * count, hipMemcpyHostToDevice,
+    S2D_CHK(kt_err, KT_EHIP, hipMemcpyAsync(c->d_poses + (size_t)first * 3, poses, sizeof(double) * 3 * count, hipMemcpyHostToDevice,
                         c->stream));
     int rc = kt_prepare(c, first, count, c->stream);
     if (rc != KT_OK) return rc;
-    KCHK(hipStreamSynchronize(c->stream));
+    S2D_CHK(kt_err, KT_EHIP, hipStreamSynchronize(c->stream));
     return KT_OK;
 }
 
 int kt_pool_device(kt_ctx *c, const double **d_ranges, const double **d_poses, int *max_scans)
 {
-    if (!c) return kfail(KT_EINVAL, "ctx is NULL");
+    if (!c) return kt_err.fail(KT_EINVAL, "ctx is NULL");
     if (d_ranges) *d_ranges = c->d_ranges;
     if (d_poses) *d_poses = c->d_poses;
     if (max_scans) *max_scans = c->max_scans;
@@ -351,10 +331,10 @@ int kt_pool_device(kt_ctx *c, const double **d_ranges, const double **d_poses, i
 int kt_match_batch_device(kt_ctx *c, int count, const int *d_query, const int *d_bbeg, const int *d_bidx,
                           int do_penalize, int do_refine, kt_result *d_res, void *hip_stream)
 {
-    if (!c || !d_query || !d_bbeg || !d_res) return kfail(KT_EINVAL, "NULL argument");
-    if (count < 0 || count > c->max_matches) return kfail(KT_EINVAL, "count exceeds max_matches");
+    if (!c || !d_query || !d_bbeg || !d_res) return kt_err.fail(KT_EINVAL, "NULL argument");
+    if (count < 0 || count > c->max_matches) return kt_err.fail(KT_EINVAL, "count exceeds max_matches");
     if (count == 0) return KT_OK;
-    if (c->max_base > 0 && !d_bidx) return kfail(KT_EINVAL, "d_base_index is NULL");
+    if (c->max_base > 0 && !d_bidx) return kt_err.fail(KT_EINVAL, "d_base_index is NULL");
     return kt_run_batch(c, count, d_query, d_bbeg, d_bidx, do_penalize ? 1 : 0, do_refine ? 1 : 0, d_res,
                         hip_stream ? (hipStream_t)hip_stream : c->stream);
 }
@@ -363,29 +343,29 @@ int kt_match_scan(kt_ctx *c, const double *q_ranges, const double q_pose[3], int
                   const double *b_poses, int do_penalize, int do_refine, kt_result *result)
 {
     if (!c || !q_ranges || !q_pose || !result || (n_base > 0 && (!b_ranges || !b_poses)))
-        return kfail(KT_EINVAL, "NULL argument");
+        return kt_err.fail(KT_EINVAL, "NULL argument");
     if (n_base < 0 || n_base > c->max_base || n_base + 1 > c->max_scans)
-        return kfail(KT_EINVAL, "n_base exceeds max_base_per_match or the scan pool");
+        return kt_err.fail(KT_EINVAL, "n_base exceeds max_base_per_match or the scan pool");
     const size_t n = (size_t)c->g.n;
     hipStream_t s = c->stream;
-    KCHK(hipMemcpyAsync(c->d_ranges, q_ranges, sizeof(double) * n, hipMemcpyHostToDevice, s));
-    KCHK(hipMemcpyAsync(c->d_poses, q_pose, sizeof(double) * 3, hipMemcpyHostToDevice, s));
+    S2D_CHK(kt_err, KT_EHIP, hipMemcpyAsync(c->d_ranges, q_ranges, sizeof(double) * n, hipMemcpyHostToDevice, s));
+    S2D_CHK(kt_err, KT_EHIP, hipMemcpyAsync(c->d_poses, q_pose, sizeof(double) * 3, hipMemcpyHostToDevice, s));
     if (n_base > 0) {
-        KCHK(hipMemcpyAsync(c->d_ranges + n, b_ranges, sizeof(double) * n * n_base, hipMemcpyHostToDevice, s));
-        KCHK(hipMemcpyAsync(c->d_poses + 3, b_poses, sizeof(double) * 3 * n_base, hipMemcpyHostToDevice, s));
+        S2D_CHK(kt_err, KT_EHIP, hipMemcpyAsync(c->d_ranges + n, b_ranges, sizeof(double) * n * n_base, hipMemcpyHostToDevice, s));
+        S2D_CHK(kt_err, KT_EHIP, hipMemcpyAsync(c->d_poses + 3, b_poses, sizeof(double) * 3 * n_base, hipMemcpyHostToDevice, s));
     }
     int rc = kt_prepare(c, 0, 1 + n_base, s);
     if (rc != KT_OK) return rc;
     std::vector<int> idx((size_t)std::max(1, n_base));
     for (int i = 0; i < n_base; ++i) idx[i] = 1 + i;
     const int q0 = 0, beg[2] = {0, n_base};
-    KCHK(hipMemcpyAsync(c->d_query, &q0, sizeof(int), hipMemcpyHostToDevice, s));
-    KCHK(hipMemcpyAsync(c->d_bbeg, beg, sizeof(int) * 2, hipMemcpyHostToDevice, s));
-    KCHK(hipMemcpyAsync(c->d_bidx, idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice, s));
+    S2D_CHK(kt_err, KT_EHIP, hipMemcpyAsync(c->d_query, &q0, sizeof(int), hipMemcpyHostToDevice, s));
+    S2D_CHK(kt_err, KT_EHIP, hipMemcpyAsync(c->d_bbeg, beg, sizeof(int) * 2, hipMemcpyHostToDevice, s));
+    S2D_CHK(kt_err, KT_EHIP, hipMemcpyAsync(c->d_bidx, idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice, s));
     rc = kt_run_batch(c, 1, c->d_query, c->d_bbeg, c->d_bidx, do_penalize ? 1 : 0, do_refine ? 1 : 0, c->d_res, s);
     if (rc != KT_OK) return rc;
-    KCHK(hipMemcpyAsync(result, c->d_res, sizeof(kt_result), hipMemcpyDeviceToHost, s));
-    KCHK(hipStreamSynchronize(s));
+    S2D_CHK(kt_err, KT_EHIP, hipMemcpyAsync(result, c->d_res, sizeof(kt_result), hipMemcpyDeviceToHost, s));
+    S2D_CHK(kt_err, KT_EHIP, hipStreamSynchronize(s));
     return KT_OK;
 }
 
@@ -399,31 +379,31 @@ size_t kt_window_exchange_words(kt_ctx *c)
 int kt_match_sharded_begin_device(kt_ctx *c, int count, const int *d_query, const int *d_bbeg, const int *d_bidx,
                                   int do_penalize, int shard, int nshards, int64_t *d_exchange, void *hip_stream)
 {
-    if (!c || !d_query || !d_bbeg || !d_exchange) return kfail(KT_EINVAL, "NULL argument");
-    if (count < 1 || count > c->slots) return kfail(KT_EINVAL, "sharded batch must hold 1 .. slots matches");
-    if (nshards < 1 || shard < 0 || shard >= nshards) return kfail(KT_EINVAL, "need 0 <= shard < nshards");
-    if (c->g.npass != 1) return kfail(KT_EINVAL, "a sharded window does not support response expansion");
-    if (c->max_base > 0 && !d_bidx) return kfail(KT_EINVAL, "d_base_index is NULL");
+    if (!c || !d_query || !d_bbeg || !d_exchange) return kt_err.fail(KT_EINVAL, "NULL argument");
+    if (count < 1 || count > c->slots) return kt_err.fail(KT_EINVAL, "sharded batch must hold 1 .. slots matches");
+    if (nshards < 1 || shard < 0 || shard >= nshards) return kt_err.fail(KT_EINVAL, "need 0 <= shard < nshards");
+    if (c->g.npass != 1) return kt_err.fail(KT_EINVAL, "a sharded window does not support response expansion");
+    if (c->max_base > 0 && !d_bidx) return kt_err.fail(KT_EINVAL, "d_base_index is NULL");
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
     int rc = kt_chunk_build(c, kt_plan_chunk(c->opt, c->g, c->max_base, count), count, d_query, d_bbeg, d_bidx, s);
     if (rc != KT_OK) return rc;
     if ((rc = kt_chunk_coarse(c, count, 0, do_penalize ? 1 : 0, shard, nshards, s)) != KT_OK) return rc;
     hipLaunchKernelGGL(kt_exchange_kernel, dim3(count), dim3(KT_THREADS), 0, s, c->g, c->d_state, c->d_resp,
                        c->d_posmax, (long long *)d_exchange, 0);
-    KCHK(hipGetLastError());
+    S2D_CHK(kt_err, KT_EHIP, hipGetLastError());
     return KT_OK;
 }
 
 int kt_match_sharded_end_device(kt_ctx *c, int count, const int *d_bbeg, const int *d_bidx, int do_penalize,
                                 int do_refine, const int64_t *d_exchange, kt_result *d_res, void *hip_stream)
 {
-    if (!c || !d_bbeg || !d_exchange || !d_res) return kfail(KT_EINVAL, "NULL argument");
-    if (count < 1 || count > c->slots) return kfail(KT_EINVAL, "sharded batch must hold 1 .. slots matches");
-    if (c->max_base > 0 && !d_bidx) return kfail(KT_EINVAL, "d_base_index is NULL");
+    if (!c || !d_bbeg || !d_exchange || !d_res) return kt_err.fail(KT_EINVAL, "NULL argument");
+    if (count < 1 || count > c->slots) return kt_err.fail(KT_EINVAL, "sharded batch must hold 1 .. slots matches");
+    if (c->max_base > 0 && !d_bidx) return kt_err.fail(KT_EINVAL, "d_base_index is NULL");
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
     hipLaunchKernelGGL(kt_exchange_kernel, dim3(count), dim3(KT_THREADS), 0, s, c->g, c->d_state, c->d_resp,
                        c->d_posmax, (long long *)d_exchange, 1);
-    KCHK(hipGetLastError());
+    S2D_CHK(kt_err, KT_EHIP, hipGetLastError());
     // the same plan as the begin call's: it depends on the context and `count` alone
     const KtChunkPlan plan = kt_plan_chunk(c->opt, c->g, c->max_base, count);
     const int rc = kt_chunk_select(c, plan, count, 0, do_refine ? 1 : 0, d_res, s);
@@ -433,40 +413,37 @@ int kt_match_sharded_end_device(kt_ctx *c, int count, const int *d_bbeg, const i
 
 int kt_copy_grid_device(kt_ctx *c, int slot, unsigned char *d_out, void *hip_stream)
 {
-    if (!c || !d_out) return kfail(KT_EINVAL, "NULL argument");
-    if (slot < 0 || slot >= c->slots) return kfail(KT_EINVAL, "slot out of range");
+    if (!c || !d_out) return kt_err.fail(KT_EINVAL, "NULL argument");
+    if (slot < 0 || slot >= c->slots) return kt_err.fail(KT_EINVAL, "slot out of range");
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    KCHK(hipMemcpyAsync(d_out, c->d_grids + (size_t)slot * c->g.grid_stride, (size_t)c->g.data_size,
+    S2D_CHK(kt_err, KT_EHIP, hipMemcpyAsync(d_out, c->d_grids + (size_t)slot * c->g.grid_stride, (size_t)c->g.data_size,
                         hipMemcpyDeviceToDevice, s));
     return KT_OK;
 }
 
 int kt_set_timing(kt_ctx *c, int enable)
 {
-    if (!c) return kfail(KT_EINVAL, "ctx is NULL");
-    c->timer.on = enable != 0;
-    return KT_OK;
+    if (!c) return kt_err.fail(KT_EINVAL, "ctx is NULL");
+    return set_timing(c->timer, enable);
 }
 
 #if defined(KT_DIAG_STAMPS)
 // diagnostic builds only: per-workgroup s_memtime stamps of kt_addscans_kernel (8 per block)
 int kt_diag_stamps(unsigned long long *out, int blocks)
 {
-    KCHK(hipDeviceSynchronize());
-    KCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(kt_diag), sizeof(unsigned long long) * 8 * blocks));
+    S2D_CHK(kt_err, KT_EHIP, hipDeviceSynchronize());
+    S2D_CHK(kt_err, KT_EHIP, hipMemcpyFromSymbol(out, HIP_SYMBOL(kt_diag), sizeof(unsigned long long) * 8 * blocks));
     return KT_OK;
 }
 #endif
 
 int kt_num_kernels(void) { return K_NUM; }
-const char *kt_kernel_name(int i) { return (i >= 0 && i < K_NUM) ? k_names[i] : ""; }
+const char *kt_kernel_name(int i) { return kernel_name(k_names, K_NUM, i); }
 
 int kt_get_kernel_times(kt_ctx *c, double *ms_out, int64_t *launches_out, int reset)
 {
-    if (!c) return kfail(KT_EINVAL, "ctx is NULL");
-    KCHK(hipDeviceSynchronize());
-    KCHK(c->timer.collect(ms_out, launches_out, reset, K_NUM));
-    return KT_OK;
+    if (!c) return kt_err.fail(KT_EINVAL, "ctx is NULL");
+    return get_kernel_times(c->timer, kt_err, ms_out, launches_out, reset, K_NUM);
 }
 
 }  // extern "C"

@@ -1,15 +1,33 @@
 // karto_graph_mirror.h -- the host mirrors of the two pose graphs (KlGraph of karto_loop_graph.h, SpaGraph of
-// spa_graph.h) rebuilt from a graph's device arrays after device-side edits: the header's counts and the edge /
-// constraint arrays in insertion order are all a mirror needs, since every other list is compile()'s function of
-// them.  Plain C++, no HIP: karto_loop_capi.hip and spa_capi.hip include it, and so does the stand-alone check
-// tests/cpp/karto_graph_mirror_check.cpp (built with -fsanitize=address,undefined).
+// spa_graph.h): the epoch that tells which of them device-side edits have left behind (EditEpoch), and a mirror
+// rebuilt from a graph's device arrays after such edits: the header's counts and the edge / constraint arrays in
+// insertion order are all a mirror needs, since every other list is compile()'s function of them.  Plain C++, no
+// HIP: karto_loop_capi.hip and spa_capi.hip include it, and so do the stand-alone checks
+// tests/cpp/karto_graph_mirror_check.cpp and tests/cpp/stage_runtime_check.cpp (built with
+// -fsanitize=address,undefined).
 #pragma once
 #include <cstddef>
+#include <vector>
 
 #include "karto_loop_graph.h"
 #include "spa_graph.h"
 
 namespace s2d {
+
+// Which mirrors are behind the device: every device edit call bumps the epoch, and graph g's host copy is current
+// only while synced[g] equals it.  seq numbers the edit calls since the last *_get_edit_info (ge_refuse's order).
+struct EditEpoch {
+    unsigned epoch = 0, seq = 0;
+    std::vector<unsigned> synced;  // per graph, 0 at first: a fresh context is current
+
+    void bump()
+    {
+        ++epoch;
+        ++seq;
+    }
+    bool current(int g) const { return synced[(size_t)g] == epoch; }
+    void mark_current(int g) { synced[(size_t)g] = epoch; }
+};
 
 // ends int[n_edges][2]: source, target.  false (the graph is left empty) when an end is no vertex or an edge joins a
 // vertex to itself -- arrays no sequence of AddVertex / AddEdge calls leaves.

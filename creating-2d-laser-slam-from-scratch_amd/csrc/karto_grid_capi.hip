@@ -11,30 +11,15 @@
 #include <string>
 #include <vector>
 
-#include "host_timing.h"
+#include "stage_runtime.h"
 #include "karto_grid_kernels.hip"
 #include "karto_internal.h"  // kg_parse_options, kg_split_rule
 
 using namespace s2d;
 
 namespace {
-thread_local std::string kg_err;
-
-int gfail(int code, const char *what, hipError_t e = hipSuccess)
-{
-    kg_err = what;
-    if (e != hipSuccess) {
-        kg_err += ": ";
-        kg_err += hipGetErrorString(e);
-    }
-    return code;
-}
-
-#define GCHK(expr)                                              \
-    do {                                                        \
-        hipError_t _e = (expr);                                 \
-        if (_e != hipSuccess) return gfail(KG_EHIP, #expr, _e); \
-    } while (0)
+thread_local StageError kg_err;
+S2D_ASSERT_STATUS_CODES(KG);
 
 double g_round(double v) { return v >= 0.0 ? std::floor(v + 0.5) : std::ceil(v - 0.5); }  // math::Round
 
@@ -62,12 +47,13 @@ struct kg_ctx {
     int8_t *d_ros = nullptr;
     hipStream_t stream = nullptr, last = nullptr;
     std::mutex mu;
+    DeviceBuffers mem;
     KernelTimer timer;
 };
 
 namespace {
 
-#define KG_LAUNCH(which, ...) S2D_TIMED_LAUNCH(c->timer, gfail, KG_EHIP, s, which, __VA_ARGS__)
+#define KG_LAUNCH(which, ...) S2D_TIMED_LAUNCH(c->timer, kg_err.fail, KG_EHIP, s, which, __VA_ARGS__)
 
 int kg_run(kg_ctx *c, int count, const double *d_ranges, const double *d_poses, kg_info *info, hipStream_t s)
 {
@@ -77,8 +63,8 @@ int kg_run(kg_ctx *c, int count, const double *d_ranges, const double *d_poses, 
     kg_info out{};
     KG_LAUNCH(G_BBOX, kg_bbox_kernel, dim3(count), dim3(KG_THREADS), 0, s, g, d_ranges, d_poses, c->d_boxes);
     KG_LAUNCH(G_REDUCE, kg_bbox_reduce_kernel, dim3(1), dim3(KG_THREADS), 0, s, count, c->d_boxes, c->d_box);
-    GCHK(hipMemcpyAsync(c->h_box, c->d_box, sizeof(double) * 4, hipMemcpyDeviceToHost, s));
-    GCHK(hipStreamSynchronize(s));  // the call's one synchronisation: the launches below are sized by the box
+    S2D_CHK(kg_err, KG_EHIP, hipMemcpyAsync(c->h_box, c->d_box, sizeof(double) * 4, hipMemcpyDeviceToHost, s));
+    S2D_CHK(kg_err, KG_EHIP, hipStreamSynchronize(s));  // the call's one synchronisation: the launches below are sized by the box
     // ComputeDimensions (Karto.h:5816-5821)
     const double w = g_round((c->h_box[2] - c->h_box[0]) * g.scale);
     const double h = g_round((c->h_box[3] - c->h_box[1]) * g.scale);
@@ -90,7 +76,7 @@ int kg_run(kg_ctx *c, int count, const double *d_ranges, const double *d_poses, 
     if (!fits || (double)out.width * (double)out.height > (double)c->max_cells) {
         out.status = KG_ERANGE;
         if (info) *info = out;
-        return gfail(KG_ERANGE, "the map has more cells than max_cells (kg_info holds its dimensions)");
+        return kg_err.fail(KG_ERANGE, "the map has more cells than max_cells (kg_info holds its dimensions)");
     }
     out.status = KG_OK;
     if (info) *info = out;
@@ -111,8 +97,8 @@ int kg_run(kg_ctx *c, int count, const double *d_ranges, const double *d_poses, 
     KG_LAUNCH(G_RAYS, kg_rays_kernel, dim3(count), dim3(KG_THREADS), 0, s, g, d_ranges, d_poses, c->d_rays,
               c->d_scans);
     if (g.split > 1) {
-        GCHK(hipMemsetAsync(c->d_pass, 0, sizeof(uint32_t) * cells, s));
-        GCHK(hipMemsetAsync(c->d_hits, 0, sizeof(uint32_t) * cells, s));
+        S2D_CHK(kg_err, KG_EHIP, hipMemsetAsync(c->d_pass, 0, sizeof(uint32_t) * cells, s));
+        S2D_CHK(kg_err, KG_EHIP, hipMemsetAsync(c->d_hits, 0, sizeof(uint32_t) * cells, s));
     }
     KG_LAUNCH(G_TRACE, kg_trace_kernel, dim3((unsigned)(ntiles * g.split)), dim3(KG_THREADS), 0, s, g, count,
               c->d_rays, c->d_scans, c->d_pass, c->d_hits);
@@ -140,26 +126,25 @@ void kg_default_params(kg_params *p)
 
 int kg_create(kg_ctx **out, const kt_laser *L, const kg_params *p, int max_scans, size_t max_cells)
 {
-    if (!out) return gfail(KG_EINVAL, "out is NULL");
+    if (!out) return kg_err.fail(KG_EINVAL, "out is NULL");
     *out = nullptr;
-    if (!L || !p) return gfail(KG_EINVAL, "NULL argument");
+    if (!L || !p) return kg_err.fail(KG_EINVAL, "NULL argument");
     if (!(p->resolution > 0) || !std::isfinite(p->resolution))
-        return gfail(KG_EINVAL, "resolution must be > 0 (the reference throws on 0)");
-    if (!(p->maximum_range > 0)) return gfail(KG_EINVAL, "maximum_range must be set (> 0): the scan's range_max");
-    if (L->n_readings < 1 || L->n_readings > 4096) return gfail(KG_EINVAL, "n_readings must be in [1, 4096]");
+        return kg_err.fail(KG_EINVAL, "resolution must be > 0 (the reference throws on 0)");
+    if (!(p->maximum_range > 0)) return kg_err.fail(KG_EINVAL, "maximum_range must be set (> 0): the scan's range_max");
+    if (L->n_readings < 1 || L->n_readings > 4096) return kg_err.fail(KG_EINVAL, "n_readings must be in [1, 4096]");
     if (!(L->range_threshold > 0) || !(L->range_threshold / p->resolution <= KG_MAX_REACH))
-        return gfail(KG_EINVAL, "range_threshold must be > 0 and at most 2^20 cells long");
+        return kg_err.fail(KG_EINVAL, "range_threshold must be > 0 and at most 2^20 cells long");
     if (max_scans < 1 || max_cells < 1 || max_cells > KG_MAX_CELLS)
-        return gfail(KG_EINVAL, "need max_scans >= 1 and 1 <= max_cells <= 2^28");
+        return kg_err.fail(KG_EINVAL, "need max_scans >= 1 and 1 <= max_cells <= 2^28");
     int force_split = 0;
     if (const char *refused = kg_parse_options(force_split, [](const char *knob) -> const char * { return getenv(knob); }))
-        return gfail(KG_EINVAL, refused);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return gfail(KG_ENODEV, "no HIP device");
+        return kg_err.fail(KG_EINVAL, refused);
+    if (!device_present()) return kg_err.fail(KG_ENODEV, "no HIP device");
     int dev = 0;
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
-        return gfail(KG_ENODEV, "no HIP device");
+        return kg_err.fail(KG_ENODEV, "no HIP device");
     kg_ctx *c = new kg_ctx;
     c->max_scans = max_scans;
     c->max_cells = max_cells;
@@ -179,21 +164,23 @@ int kg_create(kg_ctx **out, const kt_laser *L, const kg_params *p, int max_scans
     hipError_t e;
     if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamDefault)) != hipSuccess) {
         delete c;
-        return gfail(KG_EHIP, "hipStreamCreate", e);
+        return kg_err.fail(KG_EHIP, "hipStreamCreate", e);
     }
     const size_t S = (size_t)max_scans, n = (size_t)g.n, cells = (max_cells + 15) & ~(size_t)15;
-    if ((e = hipMalloc(&c->d_ranges, sizeof(double) * S * n)) != hipSuccess ||
-        (e = hipMalloc(&c->d_poses, sizeof(double) * S * 3)) != hipSuccess ||
-        (e = hipMalloc(&c->d_boxes, sizeof(double) * S * 4)) != hipSuccess ||
-        (e = hipMalloc(&c->d_box, sizeof(double) * 4)) != hipSuccess ||
-        (e = hipHostMalloc(&c->h_box, sizeof(double) * 4)) != hipSuccess ||
-        (e = hipMalloc(&c->d_rays, sizeof(int2) * S * n)) != hipSuccess ||
-        (e = hipMalloc(&c->d_scans, sizeof(KgScan) * S)) != hipSuccess ||
-        (e = hipMalloc(&c->d_pass, sizeof(uint32_t) * cells)) != hipSuccess ||
-        (e = hipMalloc(&c->d_hits, sizeof(uint32_t) * cells)) != hipSuccess ||
-        (e = hipMalloc(&c->d_state, cells)) != hipSuccess || (e = hipMalloc(&c->d_ros, cells)) != hipSuccess) {
+    DeviceBuffers &m = c->mem;
+    m.alloc(c->d_ranges, sizeof(double) * S * n);
+    m.alloc(c->d_poses, sizeof(double) * S * 3);
+    m.alloc(c->d_boxes, sizeof(double) * S * 4);
+    m.alloc(c->d_box, sizeof(double) * 4);
+    m.alloc(c->d_rays, sizeof(int2) * S * n);
+    m.alloc(c->d_scans, sizeof(KgScan) * S);
+    m.alloc(c->d_pass, sizeof(uint32_t) * cells);
+    m.alloc(c->d_hits, sizeof(uint32_t) * cells);
+    m.alloc(c->d_state, cells);
+    m.alloc(c->d_ros, cells);
+    if ((e = m.error) != hipSuccess || (e = hipHostMalloc(&c->h_box, sizeof(double) * 4)) != hipSuccess) {
         kg_destroy(c);
-        return gfail(KG_ENOMEM, "hipMalloc", e);
+        return kg_err.fail(KG_ENOMEM, "hipMalloc", e);
     }
     *out = c;
     return KG_OK;
@@ -204,9 +191,7 @@ int kg_destroy(kg_ctx *c)
     if (!c) return KG_OK;
     if (c->last) hipStreamSynchronize(c->last);
     if (c->stream) hipStreamSynchronize(c->stream);
-    void *bufs[] = {c->d_ranges, c->d_poses, c->d_boxes, c->d_box, c->d_rays, c->d_scans,
-                    c->d_pass,   c->d_hits,  c->d_state, c->d_ros};
-    for (void *b : bufs) hipFree(b);
+    c->mem.free_all();
     if (c->h_box) hipHostFree(c->h_box);
     c->timer.destroy();
     if (c->stream) hipStreamDestroy(c->stream);
@@ -221,11 +206,11 @@ int kg_build_device(kg_ctx *c, int count, const double *d_ranges, const double *
         memset(info, 0, sizeof(*info));
         info->status = KG_EINVAL;
     }
-    if (!c) return gfail(KG_EINVAL, "ctx is NULL");
+    if (!c) return kg_err.fail(KG_EINVAL, "ctx is NULL");
     std::lock_guard<std::mutex> lock(c->mu);
-    if (count == 0) return gfail(KG_EINVAL, "no scans: no grid (CreateFromScans returns NULL)");
-    if (count < 0 || count > c->max_scans) return gfail(KG_EINVAL, "count exceeds max_scans");
-    if (!d_ranges || !d_poses) return gfail(KG_EINVAL, "NULL argument");
+    if (count == 0) return kg_err.fail(KG_EINVAL, "no scans: no grid (CreateFromScans returns NULL)");
+    if (count < 0 || count > c->max_scans) return kg_err.fail(KG_EINVAL, "count exceeds max_scans");
+    if (!d_ranges || !d_poses) return kg_err.fail(KG_EINVAL, "NULL argument");
     return kg_run(c, count, d_ranges, d_poses, info, hip_stream ? (hipStream_t)hip_stream : c->stream);
 }
 
@@ -235,38 +220,38 @@ int kg_build(kg_ctx *c, int count, const double *ranges, const double *poses, kg
         memset(info, 0, sizeof(*info));
         info->status = KG_EINVAL;
     }
-    if (!c) return gfail(KG_EINVAL, "ctx is NULL");
+    if (!c) return kg_err.fail(KG_EINVAL, "ctx is NULL");
     std::lock_guard<std::mutex> lock(c->mu);
-    if (count == 0) return gfail(KG_EINVAL, "no scans: no grid (CreateFromScans returns NULL)");
-    if (count < 0 || count > c->max_scans) return gfail(KG_EINVAL, "count exceeds max_scans");
-    if (!ranges || !poses) return gfail(KG_EINVAL, "NULL argument");
+    if (count == 0) return kg_err.fail(KG_EINVAL, "no scans: no grid (CreateFromScans returns NULL)");
+    if (count < 0 || count > c->max_scans) return kg_err.fail(KG_EINVAL, "count exceeds max_scans");
+    if (!ranges || !poses) return kg_err.fail(KG_EINVAL, "NULL argument");
     hipStream_t s = c->stream;
-    GCHK(hipMemcpyAsync(c->d_ranges, ranges, sizeof(double) * (size_t)c->g.n * count, hipMemcpyHostToDevice, s));
-    GCHK(hipMemcpyAsync(c->d_poses, poses, sizeof(double) * 3 * count, hipMemcpyHostToDevice, s));
+    S2D_CHK(kg_err, KG_EHIP, hipMemcpyAsync(c->d_ranges, ranges, sizeof(double) * (size_t)c->g.n * count, hipMemcpyHostToDevice, s));
+    S2D_CHK(kg_err, KG_EHIP, hipMemcpyAsync(c->d_poses, poses, sizeof(double) * 3 * count, hipMemcpyHostToDevice, s));
     int rc = kg_run(c, count, c->d_ranges, c->d_poses, info, s);
     if (rc != KG_OK) return rc;
-    GCHK(hipStreamSynchronize(s));
+    S2D_CHK(kg_err, KG_EHIP, hipStreamSynchronize(s));
     return KG_OK;
 }
 
 int kg_get_map(kg_ctx *c, uint8_t *state, int8_t *ros, uint32_t *pass, uint32_t *hits)
 {
-    if (!c) return gfail(KG_EINVAL, "ctx is NULL");
+    if (!c) return kg_err.fail(KG_EINVAL, "ctx is NULL");
     std::lock_guard<std::mutex> lock(c->mu);
-    if (c->last) GCHK(hipStreamSynchronize(c->last));
+    if (c->last) S2D_CHK(kg_err, KG_EHIP, hipStreamSynchronize(c->last));
     const size_t cells = (size_t)c->width * c->height;
     if (cells == 0) return KG_OK;
-    if (state) GCHK(hipMemcpy(state, c->d_state, cells, hipMemcpyDeviceToHost));
-    if (ros) GCHK(hipMemcpy(ros, c->d_ros, cells, hipMemcpyDeviceToHost));
-    if (pass) GCHK(hipMemcpy(pass, c->d_pass, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost));
-    if (hits) GCHK(hipMemcpy(hits, c->d_hits, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost));
+    if (state) S2D_CHK(kg_err, KG_EHIP, hipMemcpy(state, c->d_state, cells, hipMemcpyDeviceToHost));
+    if (ros) S2D_CHK(kg_err, KG_EHIP, hipMemcpy(ros, c->d_ros, cells, hipMemcpyDeviceToHost));
+    if (pass) S2D_CHK(kg_err, KG_EHIP, hipMemcpy(pass, c->d_pass, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost));
+    if (hits) S2D_CHK(kg_err, KG_EHIP, hipMemcpy(hits, c->d_hits, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost));
     return KG_OK;
 }
 
 int kg_device_planes(kg_ctx *c, const uint8_t **d_state, const int8_t **d_ros, const uint32_t **d_pass,
                      const uint32_t **d_hits)
 {
-    if (!c) return gfail(KG_EINVAL, "ctx is NULL");
+    if (!c) return kg_err.fail(KG_EINVAL, "ctx is NULL");
     if (d_state) *d_state = c->d_state;
     if (d_ros) *d_ros = c->d_ros;
     if (d_pass) *d_pass = c->d_pass;
@@ -276,20 +261,17 @@ int kg_device_planes(kg_ctx *c, const uint8_t **d_state, const int8_t **d_ros, c
 
 int kg_set_timing(kg_ctx *c, int enable)
 {
-    if (!c) return gfail(KG_EINVAL, "ctx is NULL");
-    c->timer.on = enable != 0;
-    return KG_OK;
+    if (!c) return kg_err.fail(KG_EINVAL, "ctx is NULL");
+    return set_timing(c->timer, enable);
 }
 
 int kg_num_kernels(void) { return G_NUM; }
-const char *kg_kernel_name(int i) { return (i >= 0 && i < G_NUM) ? g_names[i] : ""; }
+const char *kg_kernel_name(int i) { return kernel_name(g_names, G_NUM, i); }
 
 int kg_get_kernel_times(kg_ctx *c, double *ms_out, int64_t *launches_out, int reset)
 {
-    if (!c) return gfail(KG_EINVAL, "ctx is NULL");
-    GCHK(hipDeviceSynchronize());
-    GCHK(c->timer.collect(ms_out, launches_out, reset, G_NUM));
-    return KG_OK;
+    if (!c) return kg_err.fail(KG_EINVAL, "ctx is NULL");
+    return get_kernel_times(c->timer, kg_err, ms_out, launches_out, reset, G_NUM);
 }
 
 }  // extern "C"

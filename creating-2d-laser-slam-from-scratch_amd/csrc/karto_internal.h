@@ -65,8 +65,9 @@ struct KtOptions {
     bool poison = false;
 };
 
-// a knob's whole value as one decimal integer ("12", "-3": no commas, no suffix, not empty) that fits an int
-inline bool parse_knob_int(const char *v, int &out)
+// a knob's whole value as one decimal integer ("12", "-3": no commas, no suffix, not empty) that fits an int.  One
+// out-of-line copy serves every knob of every context (the library has always carried it as a weak symbol).
+__attribute__((noinline)) inline bool parse_knob_int(const char *v, int &out)
 {
     char *end = nullptr;
     errno = 0;

@@ -11,31 +11,15 @@
 #include <string>
 #include <vector>
 
-#include "host_timing.h"
-#include "karto_internal.h"  // parse_knob_int (SLAM2D_POISON)
+#include "stage_runtime.h"
 #include "karto_link_commit.h"
 #include "karto_link_kernels.hip"
 
 using namespace s2d;
 
 namespace {
-thread_local std::string ke_err;
-
-int efail(int code, const char *what, hipError_t e = hipSuccess)
-{
-    ke_err = what;
-    if (e != hipSuccess) {
-        ke_err += ": ";
-        ke_err += hipGetErrorString(e);
-    }
-    return code;
-}
-
-#define ECHK(expr)                                              \
-    do {                                                        \
-        hipError_t _e = (expr);                                 \
-        if (_e != hipSuccess) return efail(KE_EHIP, #expr, _e); \
-    } while (0)
+thread_local StageError ke_err;
+S2D_ASSERT_STATUS_CODES(KE);
 
 constexpr int KE_MAX_JOBS = 1 << 20;
 constexpr int KE_MAX_MATCHES = 1 << 24;
@@ -53,39 +37,19 @@ struct ke_ctx {
     ke_link *d_links = nullptr;     // [J][K]
     ke_job_out *d_out = nullptr;    // [J]
     int *d_info = nullptr;          // [2]: the last coarse call's accepted count and status
-    hipStream_t stream = nullptr, last = nullptr;
-    hipEvent_t ev_last = nullptr;
+    StreamOrder order;
+    DeviceBuffers mem;
     KernelTimer timer;
-    std::mutex mu;
 };
 
 namespace {
 
-#define KE_LAUNCH(which, ...) S2D_TIMED_LAUNCH(c->timer, efail, KE_EHIP, s, which, __VA_ARGS__)
-
-int begin_on(ke_ctx *c, hipStream_t s)
-{
-    ECHK(hipStreamWaitEvent(s, c->ev_last, 0));
-    return KE_OK;
-}
-
-int end_on(ke_ctx *c, hipStream_t s)
-{
-    ECHK(hipEventRecord(c->ev_last, s));
-    c->last = s;
-    return KE_OK;
-}
-
-int wait_last(ke_ctx *c)
-{
-    if (c->last) ECHK(hipStreamSynchronize(c->last));
-    return KE_OK;
-}
+#define KE_LAUNCH(which, ...) S2D_TIMED_LAUNCH(c->timer, ke_err.fail, KE_EHIP, call.s, which, __VA_ARGS__)
 
 int check_rows(ke_ctx *c, int first_job, int count)
 {
-    if (!c) return efail(KE_EINVAL, "ctx is NULL");
-    if (first_job < 0 || count < 0 || first_job > c->J - count) return efail(KE_EINVAL, "job rows out of range");
+    if (!c) return ke_err.fail(KE_EINVAL, "ctx is NULL");
+    if (first_job < 0 || count < 0 || first_job > c->J - count) return ke_err.fail(KE_EINVAL, "job rows out of range");
     return KE_OK;
 }
 
@@ -119,38 +83,31 @@ void ke_node_params(ke_params *p)
 int ke_destroy(ke_ctx *c)
 {
     if (!c) return KE_OK;
-    if (c->last) hipStreamSynchronize(c->last);
-    if (c->stream) hipStreamSynchronize(c->stream);
-    void *bufs[] = {c->d_links, c->d_out, c->d_info};
-    for (void *b : bufs)
-        if (b) hipFree(b);
+    c->order.destroy();
+    c->mem.free_all();
     c->timer.destroy();
-    if (c->ev_last) hipEventDestroy(c->ev_last);
-    if (c->stream) hipStreamDestroy(c->stream);
     delete c;
     return KE_OK;
 }
 
 int ke_create(ke_ctx **out, const ke_params *params, int n_readings, int max_jobs, int max_links, int max_matches)
 {
-    if (!out) return efail(KE_EINVAL, "out is NULL");
+    if (!out) return ke_err.fail(KE_EINVAL, "out is NULL");
     *out = nullptr;
-    if (n_readings < 1 || n_readings > 4096) return efail(KE_EINVAL, "need 1 <= n_readings <= 4096");
+    if (n_readings < 1 || n_readings > 4096) return ke_err.fail(KE_EINVAL, "need 1 <= n_readings <= 4096");
     if (max_jobs < 1 || max_jobs > KE_MAX_JOBS || max_matches < 1 || max_matches > KE_MAX_MATCHES)
-        return efail(KE_EINVAL, "need 1 <= max_jobs <= 2^20 and 1 <= max_matches <= 2^24");
-    if (max_links < 1) return efail(KE_EINVAL, "need max_links >= 1");
-    if (max_links > KE_MAX_LINKS) return efail(KE_ERANGE, "max_links exceeds KE_MAX_LINKS (64)");
+        return ke_err.fail(KE_EINVAL, "need 1 <= max_jobs <= 2^20 and 1 <= max_matches <= 2^24");
+    if (max_links < 1) return ke_err.fail(KE_EINVAL, "need max_links >= 1");
+    if (max_links > KE_MAX_LINKS) return ke_err.fail(KE_ERANGE, "max_links exceeds KE_MAX_LINKS (64)");
     ke_params p;
     if (params) p = *params;
     else ke_default_params(&p);
     if (std::isnan(p.link_match_minimum_response_fine) || std::isnan(p.loop_match_minimum_response_coarse) ||
         std::isnan(p.loop_match_maximum_variance_coarse) || std::isnan(p.loop_match_minimum_response_fine))
-        return efail(KE_EINVAL, "a parameter is NaN");
+        return ke_err.fail(KE_EINVAL, "a parameter is NaN");
     int poison = 0;
-    if (const char *v = getenv("SLAM2D_POISON"))
-        if (!parse_knob_int(v, poison)) return efail(KE_EINVAL, "SLAM2D_POISON must be an integer");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return efail(KE_ENODEV, "no HIP device");
+    if (const char *why = poison_from_env(poison)) return ke_err.fail(KE_EINVAL, why);
+    if (!device_present()) return ke_err.fail(KE_ENODEV, "no HIP device");
     ke_ctx *c = new ke_ctx;
     c->J = max_jobs;
     c->K = max_links;
@@ -159,16 +116,17 @@ int ke_create(ke_ctx **out, const ke_params *params, int n_readings, int max_job
     c->params = p;
     c->link_threshold = p.link_match_minimum_response_fine - KL_TOLERANCE;  // Mapper.cpp:1141
     hipError_t e;
-    if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamDefault)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&c->ev_last, hipEventDisableTiming)) != hipSuccess) {
+    if ((e = c->order.create()) != hipSuccess) {
         ke_destroy(c);
-        return efail(KE_EHIP, "hipStreamCreate", e);
+        return ke_err.fail(KE_EHIP, "hipStreamCreate", e);
     }
     const size_t nl = sizeof(ke_link) * (size_t)max_jobs * max_links, no = sizeof(ke_job_out) * (size_t)max_jobs;
-    if ((e = hipMalloc((void **)&c->d_links, nl)) != hipSuccess || (e = hipMalloc((void **)&c->d_out, no)) != hipSuccess ||
-        (e = hipMalloc((void **)&c->d_info, sizeof(int) * 2)) != hipSuccess) {
+    c->mem.alloc(c->d_links, nl);
+    c->mem.alloc(c->d_out, no);
+    c->mem.alloc(c->d_info, sizeof(int) * 2);
+    if ((e = c->mem.error) != hipSuccess) {
         ke_destroy(c);
-        return efail(KE_ENOMEM, "hipMalloc", e);
+        return ke_err.fail(KE_ENOMEM, "hipMalloc", e);
     }
     // no row holds a result yet: n_links 0, status KE_EINVAL
     std::vector<ke_job_out> o0((size_t)max_jobs);
@@ -176,12 +134,12 @@ int ke_create(ke_ctx **out, const ke_params *params, int n_readings, int max_job
         memset(&o, 0, sizeof(o));
         o.status = KE_EINVAL;
     }
-    if ((e = hipMemsetAsync(c->d_links, poison ? 0xA5 : 0, nl, c->stream)) != hipSuccess ||
-        (e = hipMemsetAsync(c->d_info, 0, sizeof(int) * 2, c->stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(c->d_out, o0.data(), no, hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
-        (e = hipStreamSynchronize(c->stream)) != hipSuccess || (e = hipEventRecord(c->ev_last, c->stream)) != hipSuccess) {
+    if ((e = hipMemsetAsync(c->d_links, poison ? 0xA5 : 0, nl, c->order.stream)) != hipSuccess ||
+        (e = hipMemsetAsync(c->d_info, 0, sizeof(int) * 2, c->order.stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(c->d_out, o0.data(), no, hipMemcpyHostToDevice, c->order.stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(c->order.stream)) != hipSuccess || (e = hipEventRecord(c->order.ev_last, c->order.stream)) != hipSuccess) {
         ke_destroy(c);
-        return efail(KE_EHIP, "initialising the context", e);
+        return ke_err.fail(KE_EHIP, "initialising the context", e);
     }
     *out = c;
     return KE_OK;
@@ -192,18 +150,17 @@ int ke_add_edges_device(ke_ctx *c, int count, const ke_job *d_jobs, double *d_po
                         const kt_result *d_near, const kl_source *d_near_source, int n_near,
                         const kl_near_chain *d_near_chains, int chain_stride, int n_slots, int flags, void *hip_stream)
 {
-    if (!c) return efail(KE_EINVAL, "ctx is NULL");
-    if (count < 0 || count > c->J) return efail(KE_EINVAL, "count exceeds max_jobs");
+    if (!c) return ke_err.fail(KE_EINVAL, "ctx is NULL");
+    if (count < 0 || count > c->J) return ke_err.fail(KE_EINVAL, "count exceeds max_jobs");
     if (pool_scans < 1 || n_seq < 0 || n_running < 0 || n_near < 0 || chain_stride < 0 || n_slots < 0)
-        return efail(KE_EINVAL, "negative size");
-    if (flags & ~KE_WRITE_POSE) return efail(KE_EINVAL, "unknown flag");
+        return ke_err.fail(KE_EINVAL, "negative size");
+    if (flags & ~KE_WRITE_POSE) return ke_err.fail(KE_EINVAL, "unknown flag");
     if (count == 0) return KE_OK;
     if (!d_jobs || !d_pool_poses || (n_seq > 0 && !d_seq) || (n_running > 0 && !d_running) ||
         (n_near > 0 && (!d_near || !d_near_source || !d_near_chains)))
-        return efail(KE_EINVAL, "NULL argument");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    int rc = begin_on(c, s);
+        return ke_err.fail(KE_EINVAL, "NULL argument");
+    StreamCall call(c->order, ke_err, hip_stream);
+    int rc = call.begin();
     if (rc != KE_OK) return rc;
     KeAddArgs a{};
     a.count = count;
@@ -226,8 +183,8 @@ int ke_add_edges_device(ke_ctx *c, int count, const ke_job *d_jobs, double *d_po
     a.links = c->d_links;
     a.out = c->d_out;
     const unsigned blocks = (unsigned)((count + KE_JOBS_PER_BLOCK - 1) / KE_JOBS_PER_BLOCK);
-    KE_LAUNCH(E_ADD_EDGES, ke_add_edges_kernel, dim3(blocks), dim3(KE_THREADS), 0, s, a);
-    return end_on(c, s);
+    KE_LAUNCH(E_ADD_EDGES, ke_add_edges_kernel, dim3(blocks), dim3(KE_THREADS), 0, call.s, a);
+    return call.done();
 }
 
 int ke_loop_coarse_device(ke_ctx *c, int max_matches, const int *d_n_matches, const kt_result *d_coarse,
@@ -236,18 +193,17 @@ int ke_loop_coarse_device(ke_ctx *c, int max_matches, const int *d_n_matches, co
                           int *d_fine_query, int *d_fine_base_begin, int *d_fine_base_index, int *d_fine_of, int *d_n_fine,
                           double *d_tmp_ranges, double *d_tmp_poses, void *hip_stream)
 {
-    if (!c) return efail(KE_EINVAL, "ctx is NULL");
-    if (max_matches < 0 || max_matches > c->M) return efail(KE_EINVAL, "max_matches exceeds the context's");
-    if (pool_scans < 1 || capacity < 0 || base_capacity < 0) return efail(KE_EINVAL, "negative size");
-    if (tmp_first < 0 || tmp_first > INT_MAX - capacity) return efail(KE_EINVAL, "tmp_first out of range");
-    if (!d_n_matches || !d_fine_base_begin || !d_n_fine) return efail(KE_EINVAL, "NULL argument");
+    if (!c) return ke_err.fail(KE_EINVAL, "ctx is NULL");
+    if (max_matches < 0 || max_matches > c->M) return ke_err.fail(KE_EINVAL, "max_matches exceeds the context's");
+    if (pool_scans < 1 || capacity < 0 || base_capacity < 0) return ke_err.fail(KE_EINVAL, "negative size");
+    if (tmp_first < 0 || tmp_first > INT_MAX - capacity) return ke_err.fail(KE_EINVAL, "tmp_first out of range");
+    if (!d_n_matches || !d_fine_base_begin || !d_n_fine) return ke_err.fail(KE_EINVAL, "NULL argument");
     if (max_matches > 0 && (!d_coarse || !d_query || !d_base_begin || !d_base_index || !d_pool_ranges))
-        return efail(KE_EINVAL, "NULL argument");
+        return ke_err.fail(KE_EINVAL, "NULL argument");
     if (capacity > 0 && (!d_fine_query || !d_fine_of || !d_tmp_ranges || !d_tmp_poses || (base_capacity > 0 && !d_fine_base_index)))
-        return efail(KE_EINVAL, "NULL argument");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    int rc = begin_on(c, s);
+        return ke_err.fail(KE_EINVAL, "NULL argument");
+    StreamCall call(c->order, ke_err, hip_stream);
+    int rc = call.begin();
     if (rc != KE_OK) return rc;
     KeCoarseArgs a{};
     a.max_matches = max_matches;
@@ -272,19 +228,20 @@ int ke_loop_coarse_device(ke_ctx *c, int max_matches, const int *d_n_matches, co
     a.tmp_ranges = d_tmp_ranges;
     a.tmp_poses = d_tmp_poses;
     a.info = c->d_info;
-    KE_LAUNCH(E_COARSE_SCAN, ke_coarse_scan_kernel, dim3(1), dim3(KE_THREADS), 0, s, a);
-    if (capacity > 0) KE_LAUNCH(E_COARSE_WRITE, ke_coarse_write_kernel, dim3((unsigned)capacity), dim3(KE_THREADS), 0, s, a);
-    return end_on(c, s);
+    KE_LAUNCH(E_COARSE_SCAN, ke_coarse_scan_kernel, dim3(1), dim3(KE_THREADS), 0, call.s, a);
+    if (capacity > 0)
+        KE_LAUNCH(E_COARSE_WRITE, ke_coarse_write_kernel, dim3((unsigned)capacity), dim3(KE_THREADS), 0, call.s, a);
+    return call.done();
 }
 
 int ke_get_loop_info(ke_ctx *c, int *total_accepted, int *status)
 {
-    if (!c) return efail(KE_EINVAL, "ctx is NULL");
-    std::lock_guard<std::mutex> lock(c->mu);
-    int rc = wait_last(c);
+    if (!c) return ke_err.fail(KE_EINVAL, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(c->order.mu);
+    int rc = c->order.wait_last(ke_err);
     if (rc != KE_OK) return rc;
     int info[2] = {0, 0};
-    ECHK(hipMemcpy(info, c->d_info, sizeof(info), hipMemcpyDeviceToHost));
+    S2D_CHK(ke_err, KE_EHIP, hipMemcpy(info, c->d_info, sizeof(info), hipMemcpyDeviceToHost));
     if (total_accepted) *total_accepted = info[0];
     if (status) *status = info[1];
     return KE_OK;
@@ -295,18 +252,17 @@ int ke_loop_fine_device(ke_ctx *c, int count, int capacity, const int *d_n_fine,
                         const kl_loop_chain *d_loop_chains, int chain_stride, ke_closure *d_closures,
                         double *d_pool_poses, int pool_scans, int flags, void *hip_stream)
 {
-    if (!c) return efail(KE_EINVAL, "ctx is NULL");
+    if (!c) return ke_err.fail(KE_EINVAL, "ctx is NULL");
     if (count < 0 || capacity < 0 || max_matches < 0 || chain_stride < 0 || pool_scans < 0)
-        return efail(KE_EINVAL, "negative size");
-    if (max_matches > c->M) return efail(KE_EINVAL, "max_matches exceeds the context's");
-    if (flags & ~KE_WRITE_POSE) return efail(KE_EINVAL, "unknown flag");
+        return ke_err.fail(KE_EINVAL, "negative size");
+    if (max_matches > c->M) return ke_err.fail(KE_EINVAL, "max_matches exceeds the context's");
+    if (flags & ~KE_WRITE_POSE) return ke_err.fail(KE_EINVAL, "unknown flag");
     if (count == 0) return KE_OK;
     if (!d_n_fine || !d_closures || (capacity > 0 && (!d_fine || !d_fine_of || !d_source || !d_loop_chains)))
-        return efail(KE_EINVAL, "NULL argument");
-    if ((flags & KE_WRITE_POSE) && (!d_query || !d_pool_poses)) return efail(KE_EINVAL, "KE_WRITE_POSE without d_query or d_pool_poses");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    int rc = begin_on(c, s);
+        return ke_err.fail(KE_EINVAL, "NULL argument");
+    if ((flags & KE_WRITE_POSE) && (!d_query || !d_pool_poses)) return ke_err.fail(KE_EINVAL, "KE_WRITE_POSE without d_query or d_pool_poses");
+    StreamCall call(c->order, ke_err, hip_stream);
+    int rc = call.begin();
     if (rc != KE_OK) return rc;
     KeFineArgs a{};
     a.count = count;
@@ -324,25 +280,25 @@ int ke_loop_fine_device(ke_ctx *c, int count, int capacity, const int *d_n_fine,
     a.loop_chains = d_loop_chains;
     a.closures = d_closures;
     a.pool_poses = d_pool_poses;
-    KE_LAUNCH(E_FINE, ke_fine_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, s, a);
-    return end_on(c, s);
+    KE_LAUNCH(E_FINE, ke_fine_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, call.s, a);
+    return call.done();
 }
 
 int ke_close_device(ke_ctx *c, int count, const ke_job *d_jobs, const ke_closure *d_closures, const kl_closest *d_closest,
                     const double *d_pool_poses, int pool_scans, void *hip_stream)
 {
-    if (!c) return efail(KE_EINVAL, "ctx is NULL");
-    if (count < 0 || count > c->J) return efail(KE_EINVAL, "count exceeds max_jobs");
-    if (pool_scans < 1) return efail(KE_EINVAL, "negative size");
+    if (!c) return ke_err.fail(KE_EINVAL, "ctx is NULL");
+    if (count < 0 || count > c->J) return ke_err.fail(KE_EINVAL, "count exceeds max_jobs");
+    if (pool_scans < 1) return ke_err.fail(KE_EINVAL, "negative size");
     if (count == 0) return KE_OK;
-    if (!d_jobs || !d_closures || !d_closest || !d_pool_poses) return efail(KE_EINVAL, "NULL argument");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    int rc = begin_on(c, s);
+    if (!d_jobs || !d_closures || !d_closest || !d_pool_poses) return ke_err.fail(KE_EINVAL, "NULL argument");
+    StreamCall call(c->order, ke_err, hip_stream);
+    int rc = call.begin();
     if (rc != KE_OK) return rc;
-    KE_LAUNCH(E_CLOSE, ke_close_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, s, count, c->K, pool_scans, d_jobs,
+    KE_LAUNCH(E_CLOSE, ke_close_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, call.s, count, c->K, pool_scans,
+              d_jobs,
               d_closures, d_closest, d_pool_poses, c->d_links, c->d_out);
-    return end_on(c, s);
+    return call.done();
 }
 
 int ke_get_links(ke_ctx *c, int first_job, int count, ke_link *links_out, ke_job_out *jobs_out)
@@ -350,17 +306,17 @@ int ke_get_links(ke_ctx *c, int first_job, int count, ke_link *links_out, ke_job
     int rc = check_rows(c, first_job, count);
     if (rc != KE_OK) return rc;
     if (count == 0) return KE_OK;
-    std::lock_guard<std::mutex> lock(c->mu);
-    if ((rc = wait_last(c)) != KE_OK) return rc;
+    std::lock_guard<std::mutex> lock(c->order.mu);
+    if ((rc = c->order.wait_last(ke_err)) != KE_OK) return rc;
     if (links_out)
-        ECHK(hipMemcpy(links_out, c->d_links + (size_t)first_job * c->K, sizeof(ke_link) * (size_t)count * c->K, hipMemcpyDeviceToHost));
-    if (jobs_out) ECHK(hipMemcpy(jobs_out, c->d_out + first_job, sizeof(ke_job_out) * (size_t)count, hipMemcpyDeviceToHost));
+        S2D_CHK(ke_err, KE_EHIP, hipMemcpy(links_out, c->d_links + (size_t)first_job * c->K, sizeof(ke_link) * (size_t)count * c->K, hipMemcpyDeviceToHost));
+    if (jobs_out) S2D_CHK(ke_err, KE_EHIP, hipMemcpy(jobs_out, c->d_out + first_job, sizeof(ke_job_out) * (size_t)count, hipMemcpyDeviceToHost));
     return KE_OK;
 }
 
 int ke_result_device(ke_ctx *c, const ke_link **d_links, const ke_job_out **d_jobs_out, int *max_links)
 {
-    if (!c) return efail(KE_EINVAL, "ctx is NULL");
+    if (!c) return ke_err.fail(KE_EINVAL, "ctx is NULL");
     if (d_links) *d_links = c->d_links;
     if (d_jobs_out) *d_jobs_out = c->d_out;
     if (max_links) *max_links = c->K;
@@ -372,7 +328,7 @@ int ke_commit(ke_ctx *c, kl_ctx *kl, spa_ctx *spa, int first_job, int count, int
     if (n_new_edges) *n_new_edges = 0;
     int rc = check_rows(c, first_job, count);
     if (rc != KE_OK) return rc;
-    if (!kl) return efail(KE_EINVAL, "kl is NULL");
+    if (!kl) return ke_err.fail(KE_EINVAL, "kl is NULL");
     if (count == 0) return KE_OK;
     std::vector<ke_link> links((size_t)count * c->K);
     std::vector<ke_job_out> jobs((size_t)count);
@@ -399,36 +355,28 @@ int ke_commit(ke_ctx *c, kl_ctx *kl, spa_ctx *spa, int first_job, int count, int
         if (spa_add_constraint(spa, a.graph, a.from, a.to, l.diff, l.precision, nullptr) != SPA_OK) {
             why = std::string("spa_add_constraint: ") + spa_last_error();
             if (n_new_edges) *n_new_edges = fresh;
-            ke_err = why;
-            return KE_EINVAL;
+            return ke_err.fail(KE_EINVAL, why.c_str());
         }
     }
     if (n_new_edges) *n_new_edges = fresh;
-    if (!ok) {
-        ke_err = why;
-        return KE_EINVAL;
-    }
-    return KE_OK;
+    return ok ? KE_OK : ke_err.fail(KE_EINVAL, why.c_str());
 }
 
 int ke_set_timing(ke_ctx *c, int enable)
 {
-    if (!c) return efail(KE_EINVAL, "ctx is NULL");
-    std::lock_guard<std::mutex> lock(c->mu);
-    c->timer.on = enable != 0;
-    return KE_OK;
+    if (!c) return ke_err.fail(KE_EINVAL, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(c->order.mu);
+    return set_timing(c->timer, enable);
 }
 
 int ke_num_kernels(void) { return E_NUM; }
-const char *ke_kernel_name(int i) { return (i >= 0 && i < E_NUM) ? e_names[i] : ""; }
+const char *ke_kernel_name(int i) { return kernel_name(e_names, E_NUM, i); }
 
 int ke_get_kernel_times(ke_ctx *c, double *ms_out, int64_t *launches_out, int reset)
 {
-    if (!c) return efail(KE_EINVAL, "ctx is NULL");
-    std::lock_guard<std::mutex> lock(c->mu);
-    ECHK(hipDeviceSynchronize());
-    ECHK(c->timer.collect(ms_out, launches_out, reset, E_NUM));
-    return KE_OK;
+    if (!c) return ke_err.fail(KE_EINVAL, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(c->order.mu);
+    return get_kernel_times(c->timer, ke_err, ms_out, launches_out, reset, E_NUM);
 }
 
 }  // extern "C"

@@ -12,31 +12,15 @@
 #include <string>
 #include <vector>
 
-#include "host_timing.h"
-#include "karto_internal.h"  // parse_knob_int (SLAM2D_POISON)
+#include "stage_runtime.h"
 #include "karto_process_commit.h"
 #include "karto_process_kernels.hip"
 
 using namespace s2d;
 
 namespace {
-thread_local std::string kp_err;
-
-int pfail(int code, const char *what, hipError_t e = hipSuccess)
-{
-    kp_err = what;
-    if (e != hipSuccess) {
-        kp_err += ": ";
-        kp_err += hipGetErrorString(e);
-    }
-    return code;
-}
-
-#define PCHK(expr)                                              \
-    do {                                                        \
-        hipError_t _e = (expr);                                 \
-        if (_e != hipSuccess) return pfail(KP_EHIP, #expr, _e); \
-    } while (0)
+thread_local StageError kp_err;
+S2D_ASSERT_STATUS_CODES(KP);
 
 enum { P_INTAKE, P_COMPACT, P_STORE, P_APPLY, P_BIND_NEAR, P_ADVANCE, P_NUM };
 const char *const p_names[P_NUM] = {"kp_intake_kernel", "kp_compact_kernel", "kp_store_kernel",
@@ -56,34 +40,14 @@ struct kp_ctx {
     KpPending *d_pending = nullptr;  // [G]
     int *d_counts = nullptr;         // [2]: jobs, seq matches of the last intake
     int g_first = 0, count = 0, pool_scans = 0;  // the last intake's
-    hipStream_t stream = nullptr, last = nullptr;
-    hipEvent_t ev_last = nullptr;
+    StreamOrder order;
+    DeviceBuffers mem;
     KernelTimer timer;
-    std::mutex mu;
 };
 
 namespace {
 
-#define KP_LAUNCH(which, ...) S2D_TIMED_LAUNCH(c->timer, pfail, KP_EHIP, s, which, __VA_ARGS__)
-
-int begin_on(kp_ctx *c, hipStream_t s)
-{
-    PCHK(hipStreamWaitEvent(s, c->ev_last, 0));
-    return KP_OK;
-}
-
-int end_on(kp_ctx *c, hipStream_t s)
-{
-    PCHK(hipEventRecord(c->ev_last, s));
-    c->last = s;
-    return KP_OK;
-}
-
-int wait_last(kp_ctx *c)
-{
-    if (c->last) PCHK(hipStreamSynchronize(c->last));
-    return KP_OK;
-}
+#define KP_LAUNCH(which, ...) S2D_TIMED_LAUNCH(c->timer, kp_err.fail, KP_EHIP, call.s, which, __VA_ARGS__)
 
 kp_state empty_state()
 {
@@ -94,9 +58,9 @@ kp_state empty_state()
 
 int put_state(kp_ctx *c, int g, const kp_state &s)
 {
-    int rc = wait_last(c);
+    int rc = c->order.wait_last(kp_err);
     if (rc != KP_OK) return rc;
-    PCHK(hipMemcpy(c->d_state + g, &s, sizeof(s), hipMemcpyHostToDevice));
+    S2D_CHK(kp_err, KP_EHIP, hipMemcpy(c->d_state + g, &s, sizeof(s), hipMemcpyHostToDevice));
     return KP_OK;
 }
 
@@ -134,32 +98,25 @@ void kp_node_params(kp_params *p)
 int kp_destroy(kp_ctx *c)
 {
     if (!c) return KP_OK;
-    if (c->last) hipStreamSynchronize(c->last);
-    if (c->stream) hipStreamSynchronize(c->stream);
-    void *bufs[] = {c->d_pool_offset, c->d_state, c->d_rec, c->d_adv, c->d_pending, c->d_counts};
-    for (void *b : bufs)
-        if (b) hipFree(b);
+    c->order.destroy();
+    c->mem.free_all();
     c->timer.destroy();
-    if (c->ev_last) hipEventDestroy(c->ev_last);
-    if (c->stream) hipStreamDestroy(c->stream);
     delete c;
     return KP_OK;
 }
 
 int kp_create(kp_ctx **out, const kp_params *params, int n_graphs, int n_readings, int max_scans, const int *pool_offset)
 {
-    if (!out) return pfail(KP_EINVAL, "out is NULL");
+    if (!out) return kp_err.fail(KP_EINVAL, "out is NULL");
     *out = nullptr;
     kp_params p;
     if (params) p = *params;
     else kp_default_params(&p);
     KpPlan plan;
-    if (const char *why = kp_check_create(p, n_graphs, n_readings, max_scans, pool_offset, plan)) return pfail(KP_EINVAL, why);
+    if (const char *why = kp_check_create(p, n_graphs, n_readings, max_scans, pool_offset, plan)) return kp_err.fail(KP_EINVAL, why);
     int poison = 0;
-    if (const char *v = getenv("SLAM2D_POISON"))
-        if (!parse_knob_int(v, poison)) return pfail(KP_EINVAL, "SLAM2D_POISON must be an integer");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return pfail(KP_ENODEV, "no HIP device");
+    if (const char *why = poison_from_env(poison)) return kp_err.fail(KP_EINVAL, why);
+    if (!device_present()) return kp_err.fail(KP_ENODEV, "no HIP device");
     kp_ctx *c = new kp_ctx;
     c->G = n_graphs;
     c->n_readings = n_readings;
@@ -169,31 +126,31 @@ int kp_create(kp_ctx **out, const kp_params *params, int n_graphs, int n_reading
     c->pool_offset.resize((size_t)n_graphs);
     for (int g = 0; g < n_graphs; ++g) c->pool_offset[(size_t)g] = pool_offset ? pool_offset[g] : g * max_scans;
     hipError_t e;
-    if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamDefault)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&c->ev_last, hipEventDisableTiming)) != hipSuccess) {
+    if ((e = c->order.create()) != hipSuccess) {
         kp_destroy(c);
-        return pfail(KP_EHIP, "hipStreamCreate", e);
+        return kp_err.fail(KP_EHIP, "hipStreamCreate", e);
     }
     const size_t G = (size_t)n_graphs;
-    if ((e = hipMalloc((void **)&c->d_pool_offset, sizeof(int) * G)) != hipSuccess ||
-        (e = hipMalloc((void **)&c->d_state, sizeof(kp_state) * G)) != hipSuccess ||
-        (e = hipMalloc((void **)&c->d_rec, sizeof(kp_intake) * G)) != hipSuccess ||
-        (e = hipMalloc((void **)&c->d_adv, sizeof(kp_advanced) * G)) != hipSuccess ||
-        (e = hipMalloc((void **)&c->d_pending, sizeof(KpPending) * G)) != hipSuccess ||
-        (e = hipMalloc((void **)&c->d_counts, sizeof(int) * 2)) != hipSuccess) {
+    c->mem.alloc(c->d_pool_offset, sizeof(int) * G);
+    c->mem.alloc(c->d_state, sizeof(kp_state) * G);
+    c->mem.alloc(c->d_rec, sizeof(kp_intake) * G);
+    c->mem.alloc(c->d_adv, sizeof(kp_advanced) * G);
+    c->mem.alloc(c->d_pending, sizeof(KpPending) * G);
+    c->mem.alloc(c->d_counts, sizeof(int) * 2);
+    if ((e = c->mem.error) != hipSuccess) {
         kp_destroy(c);
-        return pfail(KP_ENOMEM, "hipMalloc", e);
+        return kp_err.fail(KP_ENOMEM, "hipMalloc", e);
     }
     const int fill = poison ? 0xA5 : 0;
-    if ((e = hipMemcpyAsync(c->d_pool_offset, c->pool_offset.data(), sizeof(int) * G, hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
-        (e = hipMemsetAsync(c->d_state, 0, sizeof(kp_state) * G, c->stream)) != hipSuccess ||
-        (e = hipMemsetAsync(c->d_rec, fill, sizeof(kp_intake) * G, c->stream)) != hipSuccess ||
-        (e = hipMemsetAsync(c->d_adv, fill, sizeof(kp_advanced) * G, c->stream)) != hipSuccess ||
-        (e = hipMemsetAsync(c->d_pending, 0, sizeof(KpPending) * G, c->stream)) != hipSuccess ||
-        (e = hipMemsetAsync(c->d_counts, 0, sizeof(int) * 2, c->stream)) != hipSuccess ||
-        (e = hipStreamSynchronize(c->stream)) != hipSuccess || (e = hipEventRecord(c->ev_last, c->stream)) != hipSuccess) {
+    if ((e = hipMemcpyAsync(c->d_pool_offset, c->pool_offset.data(), sizeof(int) * G, hipMemcpyHostToDevice, c->order.stream)) != hipSuccess ||
+        (e = hipMemsetAsync(c->d_state, 0, sizeof(kp_state) * G, c->order.stream)) != hipSuccess ||
+        (e = hipMemsetAsync(c->d_rec, fill, sizeof(kp_intake) * G, c->order.stream)) != hipSuccess ||
+        (e = hipMemsetAsync(c->d_adv, fill, sizeof(kp_advanced) * G, c->order.stream)) != hipSuccess ||
+        (e = hipMemsetAsync(c->d_pending, 0, sizeof(KpPending) * G, c->order.stream)) != hipSuccess ||
+        (e = hipMemsetAsync(c->d_counts, 0, sizeof(int) * 2, c->order.stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(c->order.stream)) != hipSuccess || (e = hipEventRecord(c->order.ev_last, c->order.stream)) != hipSuccess) {
         kp_destroy(c);
-        return pfail(KP_EHIP, "initialising the context", e);
+        return kp_err.fail(KP_EHIP, "initialising the context", e);
     }
     *out = c;
     return KP_OK;
@@ -204,18 +161,17 @@ int kp_intake_device(kp_ctx *c, int g_first, int count, const kp_candidate *d_ca
                      int *d_base_begin, int *d_base_index, int base_capacity, int *d_n_seq, ke_job *d_jobs,
                      kl_query *d_queries, int *d_n_jobs, kl_closest_item *d_closest_items, void *hip_stream)
 {
-    if (!c) return pfail(KP_EINVAL, "ctx is NULL");
-    if (g_first < 0 || count < 0 || g_first > c->G - count) return pfail(KP_EINVAL, "graphs out of range");
-    if (n_rows < 0 || pool_scans < 1 || base_capacity < 0) return pfail(KP_EINVAL, "negative size");
+    if (!c) return kp_err.fail(KP_EINVAL, "ctx is NULL");
+    if (g_first < 0 || count < 0 || g_first > c->G - count) return kp_err.fail(KP_EINVAL, "graphs out of range");
+    if (n_rows < 0 || pool_scans < 1 || base_capacity < 0) return kp_err.fail(KP_EINVAL, "negative size");
     if ((long long)base_capacity < (long long)count * c->plan.window_max)
-        return pfail(KP_EINVAL, "base_capacity is below count * min(scan_buffer_size, max_scans)");
+        return kp_err.fail(KP_EINVAL, "base_capacity is below count * min(scan_buffer_size, max_scans)");
     if (count == 0) return KP_OK;
     if (!d_candidates || !d_pool_ranges || !d_pool_poses || !d_query || !d_base_begin || !d_base_index || !d_n_seq || !d_n_jobs ||
         (n_rows > 0 && !d_ranges_f32))
-        return pfail(KP_EINVAL, "NULL argument");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    int rc = begin_on(c, s);
+        return kp_err.fail(KP_EINVAL, "NULL argument");
+    StreamCall call(c->order, kp_err, hip_stream);
+    int rc = call.begin();
     if (rc != KP_OK) return rc;
     KpArgs a{};
     a.g_first = g_first;
@@ -250,46 +206,48 @@ int kp_intake_device(kp_ctx *c, int g_first, int count, const kp_candidate *d_ca
     c->count = count;
     c->pool_scans = pool_scans;
     const unsigned blocks = (unsigned)((count + KP_PER_BLOCK - 1) / KP_PER_BLOCK);
-    KP_LAUNCH(P_INTAKE, kp_intake_kernel, dim3(blocks), dim3(KP_THREADS), 0, s, a);
-    KP_LAUNCH(P_COMPACT, kp_compact_kernel, dim3(1), dim3(KP_THREADS), 0, s, a);
-    KP_LAUNCH(P_STORE, kp_store_kernel, dim3((unsigned)count), dim3(KP_THREADS), 0, s, a);
-    return end_on(c, s);
+    KP_LAUNCH(P_INTAKE, kp_intake_kernel, dim3(blocks), dim3(KP_THREADS), 0, call.s, a);
+    KP_LAUNCH(P_COMPACT, kp_compact_kernel, dim3(1), dim3(KP_THREADS), 0, call.s, a);
+    KP_LAUNCH(P_STORE, kp_store_kernel, dim3((unsigned)count), dim3(KP_THREADS), 0, call.s, a);
+    return call.done();
 }
 
 int kp_apply_match_device(kp_ctx *c, const kt_result *d_seq, int n_seq, double *d_pool_poses, int pool_scans, void *hip_stream)
 {
-    if (!c) return pfail(KP_EINVAL, "ctx is NULL");
-    if (n_seq < 0) return pfail(KP_EINVAL, "negative size");
+    if (!c) return kp_err.fail(KP_EINVAL, "ctx is NULL");
+    if (n_seq < 0) return kp_err.fail(KP_EINVAL, "negative size");
     if (c->count == 0) return KP_OK;
-    if (pool_scans != c->pool_scans) return pfail(KP_EINVAL, "pool_scans differs from the last intake's");
-    if (!d_pool_poses || (n_seq > 0 && !d_seq)) return pfail(KP_EINVAL, "NULL argument");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    int rc = begin_on(c, s);
+    if (pool_scans != c->pool_scans) return kp_err.fail(KP_EINVAL, "pool_scans differs from the last intake's");
+    if (!d_pool_poses || (n_seq > 0 && !d_seq)) return kp_err.fail(KP_EINVAL, "NULL argument");
+    StreamCall call(c->order, kp_err, hip_stream);
+    int rc = call.begin();
     if (rc != KP_OK) return rc;
-    KP_LAUNCH(P_APPLY, kp_apply_kernel, dim3((unsigned)((c->count + 63) / 64)), dim3(64), 0, s, c->g_first, c->count, n_seq,
-              pool_scans, c->d_pool_offset, d_seq, c->d_rec, d_pool_poses);
-    return end_on(c, s);
+    KP_LAUNCH(P_APPLY, kp_apply_kernel, dim3((unsigned)((c->count + 63) / 64)), dim3(64), 0, call.s, c->g_first, c->count,
+              n_seq, pool_scans, c->d_pool_offset, d_seq, c->d_rec, d_pool_poses);
+    return call.done();
 }
 
 int kp_get_intake(kp_ctx *c, int first, int count, kp_intake *out, kp_advanced *advanced_out)
 {
-    if (!c) return pfail(KP_EINVAL, "ctx is NULL");
-    if (first < 0 || count < 0 || first > c->G - count) return pfail(KP_EINVAL, "records out of range");
+    if (!c) return kp_err.fail(KP_EINVAL, "ctx is NULL");
+    if (first < 0 || count < 0 || first > c->G - count) return kp_err.fail(KP_EINVAL, "records out of range");
     if (count == 0) return KP_OK;
-    std::lock_guard<std::mutex> lock(c->mu);
-    int rc = wait_last(c);
+    std::lock_guard<std::mutex> lock(c->order.mu);
+    int rc = c->order.wait_last(kp_err);
     if (rc != KP_OK) return rc;
-    if (out) PCHK(hipMemcpy(out, c->d_rec + first, sizeof(kp_intake) * (size_t)count, hipMemcpyDeviceToHost));
-    if (advanced_out) PCHK(hipMemcpy(advanced_out, c->d_adv + first, sizeof(kp_advanced) * (size_t)count, hipMemcpyDeviceToHost));
+    if (out)
+        S2D_CHK(kp_err, KP_EHIP, hipMemcpy(out, c->d_rec + first, sizeof(kp_intake) * (size_t)count, hipMemcpyDeviceToHost));
+    if (advanced_out)
+        S2D_CHK(kp_err, KP_EHIP,
+                hipMemcpy(advanced_out, c->d_adv + first, sizeof(kp_advanced) * (size_t)count, hipMemcpyDeviceToHost));
     return KP_OK;
 }
 
 int kp_commit_vertices(kp_ctx *c, kl_ctx *kl, spa_ctx *spa, int *n_added)
 {
     if (n_added) *n_added = 0;
-    if (!c) return pfail(KP_EINVAL, "ctx is NULL");
-    if (!kl) return pfail(KP_EINVAL, "kl is NULL");
+    if (!c) return kp_err.fail(KP_EINVAL, "ctx is NULL");
+    if (!kl) return kp_err.fail(KP_EINVAL, "kl is NULL");
     if (c->count == 0) return KP_OK;
     std::vector<kp_intake> recs((size_t)c->count);
     int rc = kp_get_intake(c, 0, c->count, recs.data(), nullptr);
@@ -314,37 +272,33 @@ int kp_commit_vertices(kp_ctx *c, kl_ctx *kl, spa_ctx *spa, int *n_added)
         },
         &mismatch);
     if (n_added) *n_added = n >= 0 ? n : -(n + 1);
-    if (n < 0) {
-        kp_err = mismatch ? "the graph's scan count differs from the intake's scan index" : why;
-        return KP_EINVAL;
-    }
+    if (n < 0)
+        return kp_err.fail(KP_EINVAL, mismatch ? "the graph's scan count differs from the intake's scan index" : why.c_str());
     return KP_OK;
 }
 
 int kp_bind_near_device(kp_ctx *c, ke_job *d_jobs, const kl_source *d_source, const int *d_n_matches, int max_matches, void *hip_stream)
 {
-    if (!c) return pfail(KP_EINVAL, "ctx is NULL");
-    if (max_matches < 0) return pfail(KP_EINVAL, "negative size");
+    if (!c) return kp_err.fail(KP_EINVAL, "ctx is NULL");
+    if (max_matches < 0) return kp_err.fail(KP_EINVAL, "negative size");
     if (c->count == 0) return KP_OK;
-    if (!d_jobs || !d_n_matches || (max_matches > 0 && !d_source)) return pfail(KP_EINVAL, "NULL argument");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    int rc = begin_on(c, s);
+    if (!d_jobs || !d_n_matches || (max_matches > 0 && !d_source)) return kp_err.fail(KP_EINVAL, "NULL argument");
+    StreamCall call(c->order, kp_err, hip_stream);
+    int rc = call.begin();
     if (rc != KP_OK) return rc;
-    KP_LAUNCH(P_BIND_NEAR, kp_bind_near_kernel, dim3((unsigned)((c->count + 63) / 64)), dim3(64), 0, s, c->d_counts, c->count,
-              d_jobs, d_source, d_n_matches, max_matches);
-    return end_on(c, s);
+    KP_LAUNCH(P_BIND_NEAR, kp_bind_near_kernel, dim3((unsigned)((c->count + 63) / 64)), dim3(64), 0, call.s, c->d_counts,
+              c->count, d_jobs, d_source, d_n_matches, max_matches);
+    return call.done();
 }
 
 int kp_advance_device(kp_ctx *c, const double *d_pool_poses, int pool_scans, void *hip_stream)
 {
-    if (!c) return pfail(KP_EINVAL, "ctx is NULL");
+    if (!c) return kp_err.fail(KP_EINVAL, "ctx is NULL");
     if (c->count == 0) return KP_OK;
-    if (pool_scans != c->pool_scans) return pfail(KP_EINVAL, "pool_scans differs from the last intake's");
-    if (!d_pool_poses) return pfail(KP_EINVAL, "NULL argument");
-    std::lock_guard<std::mutex> lock(c->mu);
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    int rc = begin_on(c, s);
+    if (pool_scans != c->pool_scans) return kp_err.fail(KP_EINVAL, "pool_scans differs from the last intake's");
+    if (!d_pool_poses) return kp_err.fail(KP_EINVAL, "NULL argument");
+    StreamCall call(c->order, kp_err, hip_stream);
+    int rc = call.begin();
     if (rc != KP_OK) return rc;
     KpAdvanceArgs a{};
     a.g_first = c->g_first;
@@ -359,14 +313,14 @@ int kp_advance_device(kp_ctx *c, const double *d_pool_poses, int pool_scans, voi
     a.state = c->d_state;
     a.adv = c->d_adv;
     const unsigned blocks = (unsigned)((c->count + KP_PER_BLOCK - 1) / KP_PER_BLOCK);
-    KP_LAUNCH(P_ADVANCE, kp_advance_kernel, dim3(blocks), dim3(KP_THREADS), 0, s, a);
-    return end_on(c, s);
+    KP_LAUNCH(P_ADVANCE, kp_advance_kernel, dim3(blocks), dim3(KP_THREADS), 0, call.s, a);
+    return call.done();
 }
 
 int kp_result_device(kp_ctx *c, const kp_intake **d_intake, const kp_advanced **d_advanced, const kp_state **d_state,
                      const int **d_counts)
 {
-    if (!c) return pfail(KP_EINVAL, "ctx is NULL");
+    if (!c) return kp_err.fail(KP_EINVAL, "ctx is NULL");
     if (d_intake) *d_intake = c->d_rec;
     if (d_advanced) *d_advanced = c->d_adv;
     if (d_state) *d_state = c->d_state;
@@ -376,22 +330,22 @@ int kp_result_device(kp_ctx *c, const kp_intake **d_intake, const kp_advanced **
 
 int kp_get_state(kp_ctx *c, int g, kp_state *out)
 {
-    if (!c || !out) return pfail(KP_EINVAL, "NULL argument");
-    if (g < 0 || g >= c->G) return pfail(KP_EINVAL, "graph out of range");
-    std::lock_guard<std::mutex> lock(c->mu);
-    int rc = wait_last(c);
+    if (!c || !out) return kp_err.fail(KP_EINVAL, "NULL argument");
+    if (g < 0 || g >= c->G) return kp_err.fail(KP_EINVAL, "graph out of range");
+    std::lock_guard<std::mutex> lock(c->order.mu);
+    int rc = c->order.wait_last(kp_err);
     if (rc != KP_OK) return rc;
-    PCHK(hipMemcpy(out, c->d_state + g, sizeof(kp_state), hipMemcpyDeviceToHost));
+    S2D_CHK(kp_err, KP_EHIP, hipMemcpy(out, c->d_state + g, sizeof(kp_state), hipMemcpyDeviceToHost));
     return KP_OK;
 }
 
 int kp_set_state(kp_ctx *c, int g, const kp_state *state)
 {
-    if (!c || !state) return pfail(KP_EINVAL, "NULL argument");
-    if (g < 0 || g >= c->G) return pfail(KP_EINVAL, "graph out of range");
+    if (!c || !state) return kp_err.fail(KP_EINVAL, "NULL argument");
+    if (g < 0 || g >= c->G) return kp_err.fail(KP_EINVAL, "graph out of range");
     if (!kp_state_valid(*state, c->max_scans, c->params.scan_buffer_size))
-        return pfail(KP_EINVAL, "the running scans must be a tail of the scans, at most scan_buffer_size long");
-    std::lock_guard<std::mutex> lock(c->mu);
+        return kp_err.fail(KP_EINVAL, "the running scans must be a tail of the scans, at most scan_buffer_size long");
+    std::lock_guard<std::mutex> lock(c->order.mu);
     kp_state s = *state;
     s.pad_ = 0;
     return put_state(c, g, s);
@@ -399,30 +353,27 @@ int kp_set_state(kp_ctx *c, int g, const kp_state *state)
 
 int kp_clear_graph(kp_ctx *c, int g)
 {
-    if (!c) return pfail(KP_EINVAL, "ctx is NULL");
-    if (g < 0 || g >= c->G) return pfail(KP_EINVAL, "graph out of range");
-    std::lock_guard<std::mutex> lock(c->mu);
+    if (!c) return kp_err.fail(KP_EINVAL, "ctx is NULL");
+    if (g < 0 || g >= c->G) return kp_err.fail(KP_EINVAL, "graph out of range");
+    std::lock_guard<std::mutex> lock(c->order.mu);
     return put_state(c, g, empty_state());
 }
 
 int kp_set_timing(kp_ctx *c, int enable)
 {
-    if (!c) return pfail(KP_EINVAL, "ctx is NULL");
-    std::lock_guard<std::mutex> lock(c->mu);
-    c->timer.on = enable != 0;
-    return KP_OK;
+    if (!c) return kp_err.fail(KP_EINVAL, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(c->order.mu);
+    return set_timing(c->timer, enable);
 }
 
 int kp_num_kernels(void) { return P_NUM; }
-const char *kp_kernel_name(int i) { return (i >= 0 && i < P_NUM) ? p_names[i] : ""; }
+const char *kp_kernel_name(int i) { return kernel_name(p_names, P_NUM, i); }
 
 int kp_get_kernel_times(kp_ctx *c, double *ms_out, int64_t *launches_out, int reset)
 {
-    if (!c) return pfail(KP_EINVAL, "ctx is NULL");
-    std::lock_guard<std::mutex> lock(c->mu);
-    PCHK(hipDeviceSynchronize());
-    PCHK(c->timer.collect(ms_out, launches_out, reset, P_NUM));
-    return KP_OK;
+    if (!c) return kp_err.fail(KP_EINVAL, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(c->order.mu);
+    return get_kernel_times(c->timer, kp_err, ms_out, launches_out, reset, P_NUM);
 }
 
 }  // extern "C"

@@ -15,6 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import Slam2dError
+from ._stage import TimedStage, dp as _dp, hp as _hp, library
 
 
 class KtLaser(C.Structure):
@@ -86,21 +87,22 @@ def laser(n_readings: int, minimum_angle: float, angular_resolution: float, mini
                    int(n_readings), 0)
 
 
-class ScanMatcher:
+class ScanMatcher(TimedStage):
     """ScanMatcher::Create(mapper, searchSize, resolution, smearDeviation, rangeThreshold) for a batch of
     `max_matches` concurrent matches over a pool of `max_scans` scans."""
 
+    _PREFIX = "kt"
+
     def __init__(self, laser: KtLaser, params: KtParams | None = None, max_matches: int = 1, max_scans: int = 64,
                  max_base: int = 63):
-        self.L = _lib.lib()
-        _declare(self.L)
+        self.L = library(_declare)
         self.laser = laser
         self.params = params or default_params()
         self.h = C.c_void_p()
         self._check(self.L.kt_create(C.byref(self.h), C.byref(laser), C.byref(self.params), max_matches, max_scans,
                                      max_base), "kt_create")
         info = np.zeros(10, np.int32)
-        self._check(self.L.kt_get_grid_info(self.h, info.ctypes.data_as(C.c_void_p)), "kt_get_grid_info")
+        self._check(self.L.kt_get_grid_info(self.h, _hp(info)), "kt_get_grid_info")
         keys = ["grid_size", "border", "width", "ws", "data_size", "side", "probs_ws", "half", "ksize", "max_poses"]
         self.info = {k: int(v) for k, v in zip(keys, info)}
 
@@ -111,21 +113,6 @@ class ScanMatcher:
         p.search_size, p.resolution, p.smear_deviation = float(searchSize), float(resolution), float(smearDeviation)
         return cls(laser, p, **kw)
 
-    def _check(self, rc, what):
-        if rc != 0:
-            raise Slam2dError(f"{what} failed with code {rc}: {self.L.kt_last_error().decode(errors='replace')}")
-
-    def close(self):
-        if self.h:
-            self.L.kt_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def MatchScan(self, ranges, pose, base_ranges, base_poses, doPenalize: bool = True,
                   doRefineMatch: bool = True):
         """ScanMatcher::MatchScan (Mapper.cpp:184-300): returns (mean[3], covariance[3,3], response)."""
@@ -135,9 +122,8 @@ class ScanMatcher:
         b = np.ascontiguousarray(base_ranges, np.float64).reshape(-1, n)
         bp = np.ascontiguousarray(base_poses, np.float64).reshape(-1, 3)
         r = KtResult()
-        self._check(self.L.kt_match_scan(self.h, q.ctypes.data_as(C.c_void_p), qp.ctypes.data_as(C.c_void_p),
-                                         b.shape[0], b.ctypes.data_as(C.c_void_p), bp.ctypes.data_as(C.c_void_p),
-                                         int(doPenalize), int(doRefineMatch), C.byref(r)), "kt_match_scan")
+        self._check(self.L.kt_match_scan(self.h, _hp(q), _hp(qp), b.shape[0], _hp(b), _hp(bp), int(doPenalize),
+                                         int(doRefineMatch), C.byref(r)), "kt_match_scan")
         if r.status != 0:
             raise Slam2dError(f"MatchScan: status {r.status} (an index the reference throws on)")
         return np.array(r.mean[:]), np.array(r.covariance[:]).reshape(3, 3), r.response
@@ -146,12 +132,11 @@ class ScanMatcher:
         n = self.laser.n_readings
         r = np.ascontiguousarray(ranges, np.float64).reshape(-1, n)
         p = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
-        self._check(self.L.kt_set_scans(self.h, first, r.shape[0], r.ctypes.data_as(C.c_void_p),
-                                        p.ctypes.data_as(C.c_void_p)), "kt_set_scans")
+        self._check(self.L.kt_set_scans(self.h, first, r.shape[0], _hp(r), _hp(p)), "kt_set_scans")
 
     def set_scans_device(self, first: int, count: int, d_ranges: int, d_poses: int, hip_stream: int = 0):
         self._check(self.L.kt_set_scans_device(self.h, first, count, C.c_void_p(d_ranges), C.c_void_p(d_poses),
-                                               C.c_void_p(hip_stream or None)), "kt_set_scans_device")
+                                               _dp(hip_stream)), "kt_set_scans_device")
 
     def pool_device(self):
         """(d_ranges, d_poses, max_scans): the pool's device arrays (kt_pool_device), e.g. for
@@ -164,7 +149,7 @@ class ScanMatcher:
                            doPenalize: bool = True, doRefineMatch: bool = True, hip_stream: int = 0):
         self._check(self.L.kt_match_batch_device(self.h, count, C.c_void_p(d_query), C.c_void_p(d_base_begin),
                                                  C.c_void_p(d_base_index), int(doPenalize), int(doRefineMatch),
-                                                 C.c_void_p(d_results), C.c_void_p(hip_stream or None)),
+                                                 C.c_void_p(d_results), _dp(hip_stream)),
                     "kt_match_batch_device")
 
     # ---- one window sharded over GPUs ----
@@ -177,7 +162,7 @@ class ScanMatcher:
                                    hip_stream: int = 0):
         self._check(self.L.kt_match_sharded_begin_device(self.h, count, C.c_void_p(d_query), C.c_void_p(d_base_begin),
                                                          C.c_void_p(d_base_index), int(doPenalize), shard, nshards,
-                                                         C.c_void_p(d_exchange), C.c_void_p(hip_stream or None)),
+                                                         C.c_void_p(d_exchange), _dp(hip_stream)),
                     "kt_match_sharded_begin_device")
 
     def match_sharded_end_device(self, count: int, d_base_begin: int, d_base_index: int, d_exchange: int,
@@ -186,7 +171,7 @@ class ScanMatcher:
         self._check(self.L.kt_match_sharded_end_device(self.h, count, C.c_void_p(d_base_begin),
                                                        C.c_void_p(d_base_index), int(doPenalize), int(doRefineMatch),
                                                        C.c_void_p(d_exchange), C.c_void_p(d_results),
-                                                       C.c_void_p(hip_stream or None)),
+                                                       _dp(hip_stream)),
                     "kt_match_sharded_end_device")
 
     def match_sharded(self, count: int, d_query: int, d_base_begin: int, d_base_index: int, d_results: int,
@@ -213,20 +198,15 @@ class ScanMatcher:
         import torch
         out = torch.empty(self.info["data_size"], dtype=torch.uint8, device="cuda")
         self._check(self.L.kt_copy_grid_device(self.h, slot, C.c_void_p(out.data_ptr()),
-                                               C.c_void_p(hip_stream or None)), "kt_copy_grid_device")
+                                               _dp(hip_stream)), "kt_copy_grid_device")
         torch.cuda.synchronize()
         return out.cpu().numpy().reshape(-1, self.info["ws"])
 
     def set_timing(self, on: bool):
-        self._check(self.L.kt_set_timing(self.h, 1 if on else 0), "kt_set_timing")
+        super().set_timing(on)
 
     def kernel_times(self, reset: bool = True) -> dict:
-        k = self.L.kt_num_kernels()
-        ms = np.zeros(k, np.float64)
-        n = np.zeros(k, np.int64)
-        self._check(self.L.kt_get_kernel_times(self.h, ms.ctypes.data_as(C.c_void_p), n.ctypes.data_as(C.c_void_p),
-                                               1 if reset else 0), "kt_get_kernel_times")
-        return {self.L.kt_kernel_name(i).decode(): (float(ms[i]), int(n[i])) for i in range(k)}
+        return super().kernel_times(reset)
 
 
 def shard_owns_angle(a: int, shard: int, nshards: int) -> bool:

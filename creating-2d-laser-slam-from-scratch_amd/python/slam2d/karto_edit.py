@@ -10,10 +10,9 @@ from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
-
-from . import _lib
-from ._lib import Slam2dError
+from . import _lib  # noqa: F401  (callers reach the library through the module)
+from ._lib import Slam2dError  # noqa: F401
+from ._stage import TimedStage, dp as _dp, library
 from . import karto_loop as _kl
 from . import spa as _spa
 
@@ -41,37 +40,17 @@ def _declare(L):
     L._kd_declared = True
 
 
-def _dp(addr):
-    return C.c_void_p(int(addr) or None)
-
-
-class GraphEdits:
+class GraphEdits(TimedStage):
     """Scratch for `max_rows` edit rows per call: intake records for commit_vertices_device, jobs * max_links link
     records for commit_edges_device."""
 
+    _PREFIX = "kd"
+
     def __init__(self, max_rows: int):
-        self.L = _lib.lib()
-        _declare(self.L)
+        self.L = library(_declare)
         self.max_rows = int(max_rows)
         self.h = C.c_void_p()
         self._check(self.L.kd_create(C.byref(self.h), self.max_rows), "kd_create")
-
-    def _check(self, rc, what):
-        if rc != 0:
-            err = Slam2dError(f"{what} failed with code {rc}: {self.L.kd_last_error().decode(errors='replace')}")
-            err.code = rc
-            raise err
-
-    def close(self):
-        if self.h:
-            self.L.kd_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def commit_vertices_device(self, d_intake: int, g_first: int, count: int, loop_fleet, spa_fleet=None,
                                hip_stream: int = 0):
@@ -93,13 +72,3 @@ class GraphEdits:
         a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
         self._check(self.L.kd_get_info(self.h, C.byref(a), C.byref(b), C.byref(c)), "kd_get_info")
         return a.value, b.value, c.value
-
-    def set_timing(self, enable: bool):
-        self._check(self.L.kd_set_timing(self.h, int(bool(enable))), "kd_set_timing")
-
-    def kernel_times(self, reset: bool = False) -> dict:
-        n = self.L.kd_num_kernels()
-        ms, cnt = np.zeros(n, np.float64), np.zeros(n, np.int64)
-        self._check(self.L.kd_get_kernel_times(self.h, ms.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p),
-                                               int(reset)), "kd_get_kernel_times")
-        return {self.L.kd_kernel_name(k).decode(): (float(ms[k]), int(cnt[k])) for k in range(n)}

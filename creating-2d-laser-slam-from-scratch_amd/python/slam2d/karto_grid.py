@@ -13,6 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import Slam2dError
+from ._stage import TimedStage, dp as _dp, hp as _hp, library
 from .karto import KtLaser
 
 KG_OK, KG_EINVAL, KG_ERANGE = 0, -1, -5
@@ -77,12 +78,13 @@ def _dev(x):
     return C.c_void_p(int(x))
 
 
-class OccupancyGridBuilder:
+class OccupancyGridBuilder(TimedStage):
     """OccupancyGrid::CreateFromScans for up to `max_scans` scans of `laser` and maps of up to `max_cells` cells."""
 
+    _PREFIX = "kg"
+
     def __init__(self, laser: KtLaser, params: KgParams, max_scans: int = 64, max_cells: int = 1 << 20):
-        self.L = _lib.lib()
-        _declare(self.L)
+        self.L = library(_declare)
         self.laser, self.params = laser, params
         self.max_scans, self.max_cells = int(max_scans), int(max_cells)
         self.width = self.height = 0
@@ -90,21 +92,6 @@ class OccupancyGridBuilder:
         self.h = C.c_void_p()
         self._check(self.L.kg_create(C.byref(self.h), C.byref(laser), C.byref(params), self.max_scans, self.max_cells),
                     "kg_create")
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise Slam2dError(f"{what} failed with code {rc}: {self.L.kg_last_error().decode(errors='replace')}")
-
-    def close(self):
-        if self.h:
-            self.L.kg_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _built(self, rc, info, what):
         off = np.array([info.offset_x, info.offset_y])
@@ -120,8 +107,7 @@ class OccupancyGridBuilder:
         w, h = self.width, self.height
         st, ro = np.zeros((h, w), np.uint8), np.zeros((h, w), np.int8)
         ps, ht = np.zeros((h, w), np.uint32), np.zeros((h, w), np.uint32)
-        hp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        self._check(self.L.kg_get_map(self.h, hp(st), hp(ro), hp(ps), hp(ht)), "kg_get_map")
+        self._check(self.L.kg_get_map(self.h, _hp(st), _hp(ro), _hp(ps), _hp(ht)), "kg_get_map")
         return {"width": w, "height": h, "offset": self.offset.copy(), "state": st, "ros": ro, "pass": ps, "hits": ht}
 
     def create_from_scans(self, ranges, poses) -> dict:
@@ -132,8 +118,7 @@ class OccupancyGridBuilder:
         if r.shape[0] != p.shape[0]:
             raise ValueError("ranges and poses disagree on the scan count")
         info = KgInfo()
-        rc = self.L.kg_build(self.h, r.shape[0], r.ctypes.data_as(C.c_void_p), p.ctypes.data_as(C.c_void_p),
-                             C.byref(info))
+        rc = self.L.kg_build(self.h, r.shape[0], _hp(r), _hp(p), C.byref(info))
         self._built(rc, info, "kg_build")
         return self.get_map()
 
@@ -141,8 +126,7 @@ class OccupancyGridBuilder:
         """CreateFromScans from device arrays (addresses or torch tensors), stream-ordered.  Returns the map as
         create_from_scans does, or with fetch=False only (width, height, offset): read device_planes() then."""
         info = KgInfo()
-        rc = self.L.kg_build_device(self.h, int(count), _dev(d_ranges), _dev(d_poses), C.byref(info),
-                                    C.c_void_p(hip_stream or None))
+        rc = self.L.kg_build_device(self.h, int(count), _dev(d_ranges), _dev(d_poses), C.byref(info), _dp(hip_stream))
         self._built(rc, info, "kg_build_device")
         return self.get_map() if fetch else (self.width, self.height, self.offset.copy())
 
@@ -153,12 +137,7 @@ class OccupancyGridBuilder:
         return {k: int(p.value or 0) for k, p in zip(("state", "ros", "pass", "hits"), ptrs)}
 
     def set_timing(self, on: bool):
-        self._check(self.L.kg_set_timing(self.h, 1 if on else 0), "kg_set_timing")
+        super().set_timing(on)
 
     def kernel_times(self, reset: bool = True) -> dict:
-        k = self.L.kg_num_kernels()
-        ms = np.zeros(k, np.float64)
-        n = np.zeros(k, np.int64)
-        self._check(self.L.kg_get_kernel_times(self.h, ms.ctypes.data_as(C.c_void_p), n.ctypes.data_as(C.c_void_p),
-                                               1 if reset else 0), "kg_get_kernel_times")
-        return {self.L.kg_kernel_name(i).decode(): (float(ms[i]), int(n[i])) for i in range(k)}
+        return super().kernel_times(reset)

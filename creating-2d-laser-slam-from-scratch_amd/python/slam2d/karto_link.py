@@ -12,8 +12,9 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
-from ._lib import Slam2dError
+from . import _lib  # noqa: F401  (callers reach the library through the module)
+from ._lib import Slam2dError  # noqa: F401
+from ._stage import TimedStage, dp as _dp, hp as _hp, library, params_from
 from .karto import RESULT_DTYPE as KT_RESULT_DTYPE  # noqa: F401
 
 KE_OK, KE_EINVAL, KE_EHIP, KE_ENOMEM, KE_ENODEV, KE_ERANGE, KE_SINGULAR = 0, -1, -2, -3, -4, -5, -6
@@ -87,26 +88,14 @@ def _declare(L):
     L._ke_declared = True
 
 
-def _params(which: str, **kw) -> KeParams:
-    L = _lib.lib()
-    _declare(L)
-    p = KeParams()
-    getattr(L, which)(C.byref(p))
-    for k, v in kw.items():
-        if k not in [f for f, _ in KeParams._fields_]:
-            raise TypeError(f"unknown parameter {k}")
-        setattr(p, k, v)
-    return p
-
-
 def default_params(**kw) -> KeParams:
     """ke_default_params: the Mapper defaults (0.8, 0.8, 0.4 * 0.4, 0.8); keywords override."""
-    return _params("ke_default_params", **kw)
+    return params_from(library(_declare), KeParams, "ke_default_params", **kw)
 
 
 def node_params(**kw) -> KeParams:
     """ke_node_params: mapper_params.yaml (0.1, 0.35, 3.0 * 3.0, 0.45); keywords override."""
-    return _params("ke_node_params", **kw)
+    return params_from(library(_declare), KeParams, "ke_node_params", **kw)
 
 
 def jobs(rows) -> np.ndarray:
@@ -115,45 +104,21 @@ def jobs(rows) -> np.ndarray:
     return np.ascontiguousarray(a).view(JOB_DTYPE).reshape(-1)
 
 
-def _hp(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def _dp(addr):
-    return C.c_void_p(int(addr) or None)
-
-
-class LinkStage:
+class LinkStage(TimedStage):
     """Link rows for `max_jobs` jobs of at most `max_links` records, scans of `n_readings` readings and loop batches
     of at most `max_matches` coarse matches.  Device pointers are ints."""
 
+    _PREFIX = "ke"
+
     def __init__(self, params: KeParams | None, n_readings: int, max_jobs: int, max_links: int = KE_MAX_LINKS,
                  max_matches: int = 1):
-        self.L = _lib.lib()
-        _declare(self.L)
+        self.L = library(_declare)
         self.params = params if params is not None else default_params()
         self.n_readings, self.max_jobs = int(n_readings), int(max_jobs)
         self.max_links, self.max_matches = int(max_links), int(max_matches)
         self.h = C.c_void_p()
         self._check(self.L.ke_create(C.byref(self.h), C.byref(self.params), self.n_readings, self.max_jobs,
                                      self.max_links, self.max_matches), "ke_create")
-
-    def _check(self, rc, what):
-        if rc != 0:
-            err = Slam2dError(f"{what} failed with code {rc}: {self.L.ke_last_error().decode(errors='replace')}")
-            err.code = rc
-            raise err
-
-    def close(self):
-        if self.h:
-            self.L.ke_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ------------------------------------------------------------------------------------------------ the stages
     def add_edges_device(self, count: int, d_jobs: int, d_pool_poses: int, pool_scans: int, d_seq: int, n_seq: int,
@@ -214,13 +179,3 @@ class LinkStage:
         spa_h = spa_fleet.h if spa_fleet is not None else None
         self._check(self.L.ke_commit(self.h, loop_fleet.h, spa_h, int(first_job), int(count), C.byref(n)), "ke_commit")
         return n.value
-
-    # ------------------------------------------------------------------------------------------------ timing
-    def set_timing(self, enable: bool):
-        self._check(self.L.ke_set_timing(self.h, int(bool(enable))), "ke_set_timing")
-
-    def kernel_times(self, reset: bool = False) -> dict:
-        n = self.L.ke_num_kernels()
-        ms, cnt = np.zeros(n, np.float64), np.zeros(n, np.int64)
-        self._check(self.L.ke_get_kernel_times(self.h, _hp(ms), _hp(cnt), int(reset)), "ke_get_kernel_times")
-        return {self.L.ke_kernel_name(k).decode(): (float(ms[k]), int(cnt[k])) for k in range(n)}

@@ -12,8 +12,9 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
-from ._lib import Slam2dError
+from . import _lib  # noqa: F401  (callers reach the library through the module)
+from ._lib import Slam2dError  # noqa: F401
+from ._stage import TimedStage, dp as _dp, hp as _hp, library, params_from
 from .karto import KtLaser
 
 KL_OK, KL_EINVAL, KL_EHIP, KL_ENOMEM, KL_ENODEV, KL_ERANGE = 0, -1, -2, -3, -4, -5
@@ -93,26 +94,14 @@ def _declare(L):
     L._kl_declared = True
 
 
-def _params(which: str, **kw) -> KlParams:
-    L = _lib.lib()
-    _declare(L)
-    p = KlParams()
-    getattr(L, which)(C.byref(p))
-    for k, v in kw.items():
-        if k not in [f for f, _ in KlParams._fields_]:
-            raise TypeError(f"unknown parameter {k}")
-        setattr(p, k, v)
-    return p
-
-
 def default_params(**kw) -> KlParams:
     """kl_default_params: the Mapper defaults (link 10.0, loop 4.0, chain size 10, barycentre on); keywords override."""
-    return _params("kl_default_params", **kw)
+    return params_from(library(_declare), KlParams, "kl_default_params", **kw)
 
 
 def node_params(**kw) -> KlParams:
     """kl_node_params: mapper_params.yaml (link 1.5, loop 10.0, chain size 5, barycentre on); keywords override."""
-    return _params("kl_node_params", **kw)
+    return params_from(library(_declare), KlParams, "kl_node_params", **kw)
 
 
 def queries(rows) -> np.ndarray:
@@ -121,22 +110,15 @@ def queries(rows) -> np.ndarray:
     return np.ascontiguousarray(a).view(QUERY_DTYPE).reshape(-1)
 
 
-def _hp(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def _dp(addr):
-    return C.c_void_p(int(addr) or None)
-
-
-class LoopSearchFleet:
+class LoopSearchFleet(TimedStage):
     """`max_graphs` graphs of up to `max_scans` (<= KL_MAX_SCANS) scans and `max_edges` edges, device resident, and
     result slots for `max_queries` queries per search; one workgroup answers each query."""
 
+    _PREFIX = "kl"
+
     def __init__(self, laser: KtLaser, params: KlParams | None, max_graphs: int, max_scans: int, max_edges: int,
                  max_queries: int):
-        self.L = _lib.lib()
-        _declare(self.L)
+        self.L = library(_declare)
         self.laser = laser
         self.params = params if params is not None else default_params()
         self.max_graphs, self.max_scans = int(max_graphs), int(max_scans)
@@ -144,23 +126,6 @@ class LoopSearchFleet:
         self.h = C.c_void_p()
         self._check(self.L.kl_create(C.byref(self.h), C.byref(laser), C.byref(self.params), self.max_graphs,
                                      self.max_scans, self.max_edges, self.max_queries), "kl_create")
-
-    def _check(self, rc, what):
-        if rc != 0:
-            err = Slam2dError(f"{what} failed with code {rc}: {self.L.kl_last_error().decode(errors='replace')}")
-            err.code = rc
-            raise err
-
-    def close(self):
-        if self.h:
-            self.L.kl_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ------------------------------------------------------------------------------------------------ the graph
     def add_vertex(self, g: int) -> int:
@@ -286,13 +251,3 @@ class LoopSearchFleet:
         ends, off, adj = np.zeros((m, 2), np.int32), np.zeros(n + 1, np.int32), np.zeros((2 * m, 2), np.int32)
         self._check(self.L.kl_download_graph(self.h, g, None, None, _hp(ends), _hp(off), _hp(adj)), "kl_download_graph")
         return {"n_scans": n, "n_edges": m, "ends": ends, "adj_off": off, "adj": adj}
-
-    # ------------------------------------------------------------------------------------------------ timing
-    def set_timing(self, enable: bool):
-        self._check(self.L.kl_set_timing(self.h, int(bool(enable))), "kl_set_timing")
-
-    def kernel_times(self, reset: bool = False) -> dict:
-        n = self.L.kl_num_kernels()
-        ms, cnt = np.zeros(n, np.float64), np.zeros(n, np.int64)
-        self._check(self.L.kl_get_kernel_times(self.h, _hp(ms), _hp(cnt), int(reset)), "kl_get_kernel_times")
-        return {self.L.kl_kernel_name(k).decode(): (float(ms[k]), int(cnt[k])) for k in range(n)}

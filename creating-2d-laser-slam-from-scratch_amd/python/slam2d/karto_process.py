@@ -13,8 +13,9 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
-from ._lib import Slam2dError
+from . import _lib  # noqa: F401  (callers reach the library through the module)
+from ._lib import Slam2dError  # noqa: F401
+from ._stage import TimedStage, dp as _dp, hp as _hp, library, params_from
 
 KP_OK, KP_EINVAL, KP_EHIP, KP_ENOMEM, KP_ENODEV, KP_ERANGE = 0, -1, -2, -3, -4, -5
 
@@ -84,27 +85,15 @@ def _declare(L):
     L._kp_declared = True
 
 
-def _params(which: str, **kw) -> KpParams:
-    L = _lib.lib()
-    _declare(L)
-    p = KpParams()
-    getattr(L, which)(C.byref(p))
-    for k, v in kw.items():
-        if k not in [f for f, _ in KpParams._fields_]:
-            raise TypeError(f"unknown parameter {k}")
-        setattr(p, k, v)
-    return p
-
-
 def default_params(**kw) -> KpParams:
     """kp_default_params: the Mapper defaults (3600, 0.2, DegreesToRadians(10), 20, 70, not inverted); keywords
     override."""
-    return _params("kp_default_params", **kw)
+    return params_from(library(_declare), KpParams, "kp_default_params", **kw)
 
 
 def node_params(**kw) -> KpParams:
     """kp_node_params: mapper_params.yaml (3600, 0.2, 0.174, 100, 110, not inverted); keywords override."""
-    return _params("kp_node_params", **kw)
+    return params_from(library(_declare), KpParams, "kp_node_params", **kw)
 
 
 def candidates(rows, times, odoms) -> np.ndarray:
@@ -117,21 +106,14 @@ def candidates(rows, times, odoms) -> np.ndarray:
     return c
 
 
-def _hp(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def _dp(addr):
-    return C.c_void_p(int(addr) or None)
-
-
-class ProcessStage:
+class ProcessStage(TimedStage):
     """The intake state of `n_graphs` graphs of up to `max_scans` scans of `n_readings` readings; graph g's scan i is
     pool slot pool_offset[g] + i (None: g * max_scans).  Device pointers are ints."""
 
+    _PREFIX = "kp"
+
     def __init__(self, params: KpParams | None, n_graphs: int, n_readings: int, max_scans: int, pool_offset=None):
-        self.L = _lib.lib()
-        _declare(self.L)
+        self.L = library(_declare)
         self.params = params if params is not None else default_params()
         self.n_graphs, self.n_readings, self.max_scans = int(n_graphs), int(n_readings), int(max_scans)
         off = None
@@ -142,23 +124,6 @@ class ProcessStage:
         self.h = C.c_void_p()
         self._check(self.L.kp_create(C.byref(self.h), C.byref(self.params), self.n_graphs, self.n_readings,
                                      self.max_scans, _hp(off) if off is not None else None), "kp_create")
-
-    def _check(self, rc, what):
-        if rc != 0:
-            err = Slam2dError(f"{what} failed with code {rc}: {self.L.kp_last_error().decode(errors='replace')}")
-            err.code = rc
-            raise err
-
-    def close(self):
-        if self.h:
-            self.L.kp_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ------------------------------------------------------------------------------------------------ the stages
     def intake_device(self, g_first: int, count: int, d_candidates: int, d_ranges_f32: int, n_rows: int,
@@ -216,13 +181,3 @@ class ProcessStage:
 
     def clear_graph(self, g: int):
         self._check(self.L.kp_clear_graph(self.h, int(g)), "kp_clear_graph")
-
-    # ------------------------------------------------------------------------------------------------ timing
-    def set_timing(self, enable: bool):
-        self._check(self.L.kp_set_timing(self.h, int(bool(enable))), "kp_set_timing")
-
-    def kernel_times(self, reset: bool = False) -> dict:
-        n = self.L.kp_num_kernels()
-        ms, cnt = np.zeros(n, np.float64), np.zeros(n, np.int64)
-        self._check(self.L.kp_get_kernel_times(self.h, _hp(ms), _hp(cnt), int(reset)), "kp_get_kernel_times")
-        return {self.L.kp_kernel_name(k).decode(): (float(ms[k]), int(cnt[k])) for k in range(n)}

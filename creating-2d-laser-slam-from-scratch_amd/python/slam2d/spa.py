@@ -17,6 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import Slam2dError
+from ._stage import Stage, dp as _dp, hp as _hp, library
 
 SPA_OK, SPA_EINVAL, SPA_ERANGE = 0, -1, -5
 SPA_NOT_RUN, SPA_NO_FIXED, SPA_DISCONNECTED, SPA_NOT_POSDEF, SPA_FACTOR_RANGE = -100, 1, 2, 3, 4
@@ -194,38 +195,20 @@ def precision_of(covariance) -> np.ndarray:
     return m
 
 
-def _hp(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-class SpaFleet:
+class SpaFleet(Stage):
     """A batch of `max_graphs` independent pose graphs, device resident; one workgroup optimises each.
     `max_factor_blocks` is the direct solve's room per graph in 3 x 3 blocks (see envelope_blocks); 0 serves the PCG
     mode only."""
 
+    _PREFIX = "spa"
+
     def __init__(self, max_graphs: int, max_nodes: int, max_constraints: int, max_factor_blocks: int = 0):
-        self.L = _lib.lib()
-        _declare(self.L)
+        self.L = library(_declare)
         self.max_graphs, self.max_nodes, self.max_constraints = int(max_graphs), int(max_nodes), int(max_constraints)
         self.max_factor_blocks = int(max_factor_blocks)
         self.h = C.c_void_p()
         self._check(self.L.spa_create_ex(C.byref(self.h), self.max_graphs, self.max_nodes, self.max_constraints,
                                          self.max_factor_blocks), "spa_create_ex")
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise Slam2dError(f"{what} failed with code {rc}: {self.L.spa_last_error().decode(errors='replace')}")
-
-    def close(self):
-        if self.h:
-            self.L.spa_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def add_node(self, g: int, id_: int, pose):
         p = np.ascontiguousarray(pose, np.float64).reshape(3)
@@ -308,16 +291,14 @@ class SpaFleet:
     # ------------------------------------------------------------------------------------------------ device edits
     def edit_nodes_device(self, count: int, d_rows: int, d_mask: int = 0, d_status: int = 0, hip_stream: int = 0):
         """spa_edit_nodes_device: `count` spa_node_row rows (NODE_ROW_DTYPE) at device address d_rows."""
-        v = lambda a: C.c_void_p(int(a) or None)  # noqa: E731
-        self._check(self.L.spa_edit_nodes_device(self.h, int(count), v(d_rows), v(d_mask), v(d_status), v(hip_stream)),
-                    "spa_edit_nodes_device")
+        self._check(self.L.spa_edit_nodes_device(self.h, int(count), _dp(d_rows), _dp(d_mask), _dp(d_status),
+                                                 _dp(hip_stream)), "spa_edit_nodes_device")
 
     def edit_constraints_device(self, count: int, d_rows: int, d_mask: int = 0, d_added: int = 0, d_status: int = 0,
                                 hip_stream: int = 0):
         """spa_edit_constraints_device: `count` spa_con_row rows (CON_ROW_DTYPE) at device address d_rows."""
-        v = lambda a: C.c_void_p(int(a) or None)  # noqa: E731
-        self._check(self.L.spa_edit_constraints_device(self.h, int(count), v(d_rows), v(d_mask), v(d_added), v(d_status),
-                                                       v(hip_stream)), "spa_edit_constraints_device")
+        self._check(self.L.spa_edit_constraints_device(self.h, int(count), _dp(d_rows), _dp(d_mask), _dp(d_added),
+                                                       _dp(d_status), _dp(hip_stream)), "spa_edit_constraints_device")
 
     def edit_info(self):
         """(rows refused since the last call, status of the first); waits."""
