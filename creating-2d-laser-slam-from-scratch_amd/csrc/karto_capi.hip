@@ -17,10 +17,12 @@ namespace {
 thread_local StageError kt_err;
 S2D_ASSERT_STATUS_CODES(KT);
 
-enum { K_PREPARE, K_BEGIN, K_BUILD, K_COARSE, K_SELECT, K_FINE, K_CLEAR, K_NUM };
+enum { K_PREPARE, K_BEGIN, K_BUILD, K_COARSE, K_SELECT, K_FINE, K_CLEAR, K_REFRESH, K_NUM };
 const char *const k_names[K_NUM] = {"kt_prepare_kernel", "kt_begin_kernel", "kt_build_kernel", "kt_coarse_kernel",
-                                    "kt_select_kernel",  "kt_fine_kernel",  "kt_build_kernel<1> (clear)"};
+                                    "kt_select_kernel",  "kt_fine_kernel",  "kt_build_kernel<1> (clear)",
+                                    "kt_refresh_kernel"};
 static_assert(K_NUM <= KernelTimer::MAX_KERNELS, "the timer's accumulators");
+static_assert(KT_REFRESH_MAX_ROWS == REFRESH_MAX_ROWS, "the plan header's row limit");
 }  // namespace
 
 struct kt_ctx {
@@ -29,6 +31,9 @@ struct kt_ctx {
     KtGeom g{};
     int max_matches = 0, max_scans = 0, max_base = 0;
     KtOptions opt{};         // the environment's knobs, read once at kt_create
+    RefreshOptions refresh_opt{};
+    DeviceEditEpoch refresh;  // kt_refresh_device's refused rows (its words and call numbers only)
+    int num_cus = 1;
     int slots = 0;           // match slots resident at once (kt_run_batch chunk)
     size_t prepare_lds = 0;  // kt_prepare_kernel's dynamic LDS
     int *d_scratch = nullptr, *d_dirty = nullptr, *d_dirty_cnt = nullptr;
@@ -210,12 +215,21 @@ int kt_create(kt_ctx **out, const kt_laser *laser, const kt_params *params, int 
     KtOptions opt;
     const char *refused = kt_parse_options(opt, [](const char *knob) -> const char * { return getenv(knob); });
     if (refused) return kt_err.fail(KT_EINVAL, refused);
+    RefreshOptions refresh_opt;
+    if ((refused = refresh_parse_options(refresh_opt, [](const char *knob) -> const char * { return getenv(knob); })))
+        return kt_err.fail(KT_EINVAL, refused);
     KtGeom g;
     std::vector<unsigned char> kernel;
     const int rc = kt_geometry(*laser, p, opt, g, kernel, refused);
     if (rc != KT_OK) return kt_err.fail(rc, refused);
     if (!device_present()) return kt_err.fail(KT_ENODEV, "no HIP device");
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
+        return kt_err.fail(KT_ENODEV, "no HIP device");
     kt_ctx *c = new kt_ctx;
+    c->refresh_opt = refresh_opt;
+    c->num_cus = std::max(1, prop.multiProcessorCount);
     c->laser = *laser;
     c->params = p;
     c->g = g;
@@ -252,6 +266,7 @@ int kt_create(kt_ctx **out, const kt_laser *laser, const kt_params *params, int 
     m.alloc(c->d_bbeg, sizeof(int) * 2);
     m.alloc(c->d_bidx, sizeof(int) * std::max<size_t>(1, (size_t)max_base_per_match));
     m.alloc(c->d_res, sizeof(kt_result));
+    m.alloc(c->refresh.d_info, sizeof(unsigned long long) * 2);
     if (kt_binned_eligible(opt, g, max_base_per_match)) {
         m.alloc(c->d_scratch, sizeof(int) * M * std::max<size_t>(1, (size_t)max_base_per_match) * n);
         m.alloc(c->d_dirty, sizeof(int) * M * (size_t)g.ntiles);
@@ -267,8 +282,16 @@ int kt_create(kt_ctx **out, const kt_laser *laser, const kt_params *params, int 
         kt_destroy(c);
         return kt_err.fail(KT_EHIP, "hipFuncSetAttribute(kt_prepare_kernel)", e);
     }
+    // kt_refresh_kernel keeps the rows' prefix sum (at most 16 KB) behind the same arrays
+    if (kt_refresh_lds(plan.prepare_lds, REFRESH_MAX_ROWS) + 64 > 65536 &&
+        (e = hipFuncSetAttribute((const void *)kt_refresh_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)kt_refresh_lds(plan.prepare_lds, REFRESH_MAX_ROWS))) != hipSuccess) {
+        kt_destroy(c);
+        return kt_err.fail(KT_EHIP, "hipFuncSetAttribute(kt_refresh_kernel)", e);
+    }
     if ((e = hipMemsetAsync(c->d_grids, 0, g.grid_stride * M, c->stream)) != hipSuccess ||
         (e = hipMemsetAsync(c->d_npts, 0, sizeof(int) * S, c->stream)) != hipSuccess ||
+        (e = c->refresh.reset_async(c->stream)) != hipSuccess ||
         (e = hipMemcpyAsync(c->d_kernel, kernel.data(), kernel.size(), hipMemcpyHostToDevice, c->stream)) !=
             hipSuccess ||
         (e = hipStreamSynchronize(c->stream)) != hipSuccess) {
@@ -325,6 +348,52 @@ int kt_pool_device(kt_ctx *c, const double **d_ranges, const double **d_poses, i
     if (d_ranges) *d_ranges = c->d_ranges;
     if (d_poses) *d_poses = c->d_poses;
     if (max_scans) *max_scans = c->max_scans;
+    return KT_OK;
+}
+
+int kt_refresh_device(kt_ctx *c, int n_rows, const void *d_rows, const double *d_pool_ranges, const double *d_pool_poses,
+                      int pool_scans, void *hip_stream)
+{
+    if (!c) return kt_err.fail(KT_EINVAL, "ctx is NULL");
+    if (n_rows < 0 || pool_scans < 0) return kt_err.fail(KT_EINVAL, "negative count");
+    if (n_rows > KT_REFRESH_MAX_ROWS) return kt_err.fail(KT_ERANGE, "more than KT_REFRESH_MAX_ROWS (4096) rows");
+    if (n_rows == 0) return KT_OK;
+    if (!d_rows || !d_pool_ranges || !d_pool_poses) return kt_err.fail(KT_EINVAL, "NULL argument");
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    const int limit = std::min(c->max_scans, pool_scans);
+    if (limit == 0) return KT_OK;  // no row can name a slot: nothing to launch (and nothing to refuse into)
+    c->refresh.bump();
+    // the host knows no row, so the launch is sized by what the rows can name at most
+    const int grid = refresh_grid(c->refresh_opt, c->num_cus, refresh_bound(n_rows, limit));
+    const KtRefresh r{(const int2 *)d_rows, d_pool_ranges, d_pool_poses, c->d_ranges, c->d_poses, c->refresh.d_info, n_rows,
+                      limit, (d_pool_ranges != c->d_ranges ? 1 : 0) | (d_pool_poses != c->d_poses ? 2 : 0), c->refresh.seq,
+                      (int)kt_refresh_prefix_offset(c->prepare_lds)};
+    KT_LAUNCH(K_REFRESH, kt_refresh_kernel, dim3((unsigned)grid), dim3(KT_THREADS), kt_refresh_lds(c->prepare_lds, n_rows), s,
+              c->g, c->pool(), r);
+    return KT_OK;
+}
+
+int kt_get_refresh_info(kt_ctx *c, int *n_refused, int *first_status)
+{
+    if (!c) return kt_err.fail(KT_EINVAL, "ctx is NULL");
+    S2D_CHK(kt_err, KT_EHIP, hipDeviceSynchronize());
+    return c->refresh.read_and_reset(kt_err, n_refused, first_status);
+}
+
+int kt_get_prepared(kt_ctx *c, int slot, int *npts, double *pts, double *loc, unsigned char *bad, int *evt)
+{
+    if (!c) return kt_err.fail(KT_EINVAL, "ctx is NULL");
+    if (slot < 0 || slot >= c->max_scans) return kt_err.fail(KT_EINVAL, "scan slot out of range");
+    S2D_CHK(kt_err, KT_EHIP, hipDeviceSynchronize());
+    int k = 0;
+    S2D_CHK(kt_err, KT_EHIP, hipMemcpy(&k, c->d_npts + slot, sizeof(int), hipMemcpyDeviceToHost));
+    if (k < 0 || k > c->g.n) return kt_err.fail(KT_EHIP, "the slot's point count is out of range");
+    if (npts) *npts = k;
+    const size_t at = (size_t)slot * c->g.n;
+    if (k > 0 && pts) S2D_CHK(kt_err, KT_EHIP, hipMemcpy(pts, c->d_pts + at, sizeof(double2) * k, hipMemcpyDeviceToHost));
+    if (k > 0 && loc) S2D_CHK(kt_err, KT_EHIP, hipMemcpy(loc, c->d_loc + at, sizeof(double2) * k, hipMemcpyDeviceToHost));
+    if (k > 0 && bad) S2D_CHK(kt_err, KT_EHIP, hipMemcpy(bad, c->d_bad + at, (size_t)k, hipMemcpyDeviceToHost));
+    if (k > 0 && evt) S2D_CHK(kt_err, KT_EHIP, hipMemcpy(evt, c->d_evt + at, sizeof(int2) * k, hipMemcpyDeviceToHost));
     return KT_OK;
 }
 

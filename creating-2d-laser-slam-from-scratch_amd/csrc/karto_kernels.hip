@@ -37,7 +37,9 @@
 
 #include "../../include/slam2d/karto.h"
 #include "detmath.h"
-#include "karto_internal.h"  // KtGeom, KT_THREADS and the other sizes the host's launch plan shares
+#include "graph_edit_device.h"  // ge_refuse, ge_exscan_array (kt_refresh_kernel)
+#include "karto_internal.h"     // KtGeom, KT_THREADS and the other sizes the host's launch plan shares
+#include "scan_refresh_plan.h"  // REFRESH_MAX_ROWS
 
 namespace s2d {
 
@@ -151,21 +153,19 @@ __device__ __forceinline__ void kt_inv_rot(double h, double r[6])
 // =================================================================================================
 // kt_prepare_kernel: pooled scans -> point readings, local points, reset events
 // =================================================================================================
-__global__ void __launch_bounds__(KT_THREADS)
-kt_prepare_kernel(KtGeom g, KtPool P, int first)
+// One scan by one workgroup: pool slot s from the readings raw[n] and the pose (px, py, ph).  kt_smem: the kernel's
+// dynamic LDS (KtChunkPlan::prepare_lds); sw, s_nev: 4 + 1 ints of LDS.  A caller that runs it again puts a barrier
+// between the runs (the last loop reads sev).
+__device__ __forceinline__ void kt_prepare_scan(const KtGeom &g, const KtPool &P, int s, const double *__restrict__ raw,
+                                                double px, double py, double ph, unsigned char *kt_smem, int *sw,
+                                                int &s_nev)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char kt_smem[];
     double2 *spts = reinterpret_cast<double2 *>(kt_smem);       // [n]
     int *sev = reinterpret_cast<int *>(spts + g.n);              // [n] reset events
     int *snext = sev + g.n;                                      // [n] next point beyond 0.1 m
-    __shared__ int sw[4];
-    __shared__ int s_nev;
 
-    const int s = first + blockIdx.x;
     const int tid = threadIdx.x;
     const int n = g.n;
-    const double *raw = P.ranges + (size_t)s * n;
-    const double px = P.poses[3 * s], py = P.poses[3 * s + 1], ph = P.poses[3 * s + 2];
 
     // order-preserving compaction of the readings InRange(r, minimumRange, rangeThreshold)
     const int chunk = (n + KT_THREADS - 1) / KT_THREADS;
@@ -236,6 +236,91 @@ kt_prepare_kernel(KtGeom g, KtPool P, int first)
             else lo = mid + 1;
         }
         evt[j] = lo < nev ? make_int2(sev[lo], lo > 0 ? sev[lo - 1] : 0) : make_int2(-1, -1);
+    }
+}
+
+__global__ void __launch_bounds__(KT_THREADS)
+kt_prepare_kernel(KtGeom g, KtPool P, int first)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char kt_smem[];
+    __shared__ int sw[4];
+    __shared__ int s_nev;
+
+    const int s = first + blockIdx.x;
+    kt_prepare_scan(g, P, s, P.ranges + (size_t)s * g.n, P.poses[3 * s], P.poses[3 * s + 1], P.poses[3 * s + 2], kt_smem,
+                    sw, s_nev);
+}
+
+// =================================================================================================
+// kt_refresh_kernel: kt_prepare_kernel's work for the pool slots that rows of device memory name
+// =================================================================================================
+// Row i = {first slot, count} (kl_refresh_device's resolved rows): slot s is prepared from row s of `ranges` and
+// `poses`.  copy bit 0 / bit 1: `ranges` / `poses` is not the pool's own array, and the slot's readings / pose are
+// stored into the pool as well, as kt_set_scans_device's copies do.  The plan is kl_refresh_kernel's (karto_loop_kernels.hip): the
+// host knows no count, so the launch has a fixed size, every workgroup builds the prefix sum of the rows' counts in
+// LDS and the workgroups take the scans of that list by a grid-stride loop, located by bisection -- here one
+// WORKGROUP per scan, kt_prepare_kernel's shape.  A row with count <= 0 is skipped; one outside [0, limit] is
+// refused, written nowhere and counted by workgroup 0.
+struct KtRefresh {
+    const int2 *rows;
+    const double *ranges, *poses;
+    double *pool_ranges, *pool_poses;  // the pool's arrays, writable
+    unsigned long long *info;          // ge_refuse's two words
+    int n_rows, limit, copy;
+    unsigned seq;
+    int off_bytes;  // where the prefix sum starts in the dynamic LDS: behind kt_prepare_scan's arrays
+};
+
+// kt_refresh_kernel's dynamic LDS: kt_prepare_scan's arrays, then n_rows + 1 ints of prefix sum.  The prefix is sized by
+// the call's rows and not by REFRESH_MAX_ROWS, so that a fleet-sized call keeps kt_prepare_kernel's workgroups per CU.
+__host__ __device__ inline size_t kt_refresh_prefix_offset(size_t prepare_lds) { return (prepare_lds + 15) & ~(size_t)15; }
+__host__ __device__ inline size_t kt_refresh_lds(size_t prepare_lds, int n_rows)
+{
+    return kt_refresh_prefix_offset(prepare_lds) + sizeof(int) * ((size_t)n_rows + 1);
+}
+
+__global__ void __launch_bounds__(KT_THREADS)
+kt_refresh_kernel(KtGeom g, KtPool P, KtRefresh R)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char kt_smem[];
+    int *s_off = reinterpret_cast<int *>(kt_smem + R.off_bytes);  // [n_rows + 1]
+    __shared__ int sw[4];
+    __shared__ int s_nev;
+    static_assert(KT_THREADS == GE_THREADS, "ge_exscan_array strides by GE_THREADS");
+
+    const int tid = threadIdx.x, n = g.n;
+    for (int i = tid; i < R.n_rows; i += KT_THREADS) {
+        const int2 r = R.rows[i];
+        int count = r.y > 0 ? r.y : 0;
+        if (count > 0 && (r.x < 0 || r.x > R.limit - count)) {
+            count = 0;
+            if (blockIdx.x == 0) ge_refuse(R.info, R.seq, i, KT_EINVAL);
+        }
+        s_off[i] = count;
+    }
+    __syncthreads();
+    const int total = ge_exscan_array(s_off, R.n_rows, sw);
+    for (int w = blockIdx.x; w < total; w += gridDim.x) {
+        int lo = 0, hi = R.n_rows - 1;  // the last row whose offset is <= w
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (s_off[mid] <= w) lo = mid;
+            else hi = mid - 1;
+        }
+        const int s = R.rows[lo].x + (w - s_off[lo]);
+        const double *raw = R.ranges + (size_t)s * n;
+        const double px = R.poses[3 * (size_t)s], py = R.poses[3 * (size_t)s + 1], ph = R.poses[3 * (size_t)s + 2];
+        if (R.copy & 1)
+            for (int i = tid; i < n; i += KT_THREADS) R.pool_ranges[(size_t)s * n + i] = raw[i];
+        if (R.copy & 2) {
+            if (tid == 0) {
+                R.pool_poses[3 * (size_t)s] = px;
+                R.pool_poses[3 * (size_t)s + 1] = py;
+                R.pool_poses[3 * (size_t)s + 2] = ph;
+            }
+        }
+        kt_prepare_scan(g, P, s, raw, px, py, ph, kt_smem, sw, s_nev);
+        __syncthreads();
     }
 }
 

@@ -15,6 +15,7 @@
 #include "stage_runtime.h"
 #include "karto_graph_mirror.h"
 #include "karto_loop_graph.h"
+#include "scan_refresh_plan.h"
 #include "karto_loop_kernels.hip"
 
 using namespace s2d;
@@ -27,10 +28,14 @@ constexpr int KL_MAX_GRAPHS = 1 << 16;
 constexpr int KL_MAX_EDGES = 1 << 20;
 constexpr int KL_MAX_QUERIES = 1 << 20;
 
-enum { L_REFERENCE, L_SEARCH, L_CLOSEST, L_EMIT_SCAN, L_EMIT_WRITE, L_EDIT_VERTICES, L_EDIT_EDGES, L_NUM };
+enum { L_REFERENCE, L_SEARCH, L_CLOSEST, L_EMIT_SCAN, L_EMIT_WRITE, L_REFRESH, L_EDIT_VERTICES, L_EDIT_EDGES, L_NUM };
 const char *const l_names[L_NUM] = {"kl_reference_kernel", "kl_search_kernel", "kl_closest_kernel", "kl_emit_scan_kernel",
-                                    "kl_emit_write_kernel", "kl_edit_vertices_kernel", "kl_edit_edges_kernel"};
+                                    "kl_emit_write_kernel", "kl_refresh_kernel", "kl_edit_vertices_kernel",
+                                    "kl_edit_edges_kernel"};
 static_assert(L_NUM <= KernelTimer::MAX_KERNELS, "the timer's accumulators");
+static_assert(KL_REFRESH_MAX_ROWS == REFRESH_MAX_ROWS, "the plan header's row limit");
+static_assert(KL_WAVES == REFRESH_WAVES, "the plan header's scans per workgroup");
+static_assert(sizeof(kl_refresh_span) == sizeof(int2) && sizeof(kl_refresh_row) == 16, "the row layouts");
 }  // namespace
 
 struct kl_ctx {
@@ -42,6 +47,9 @@ struct kl_ctx {
     std::vector<char> dirty;  // per graph: edited since the last upload
     bool any_dirty = false;
     DeviceEditEpoch edit;  // device edits: which host copies are behind
+    DeviceEditEpoch refresh;  // kl_refresh_device's refused rows (its words and call numbers only)
+    RefreshOptions refresh_opt;
+    int num_cus = 1;
     int2 *d_ends = nullptr;
     KlDev dev{};
     KlHdr *d_hdr = nullptr;
@@ -224,8 +232,17 @@ int kl_create(kl_ctx **out, const kt_laser *laser, const kl_params *params, int 
         return kl_err.fail(KL_EINVAL, "the distances must be finite and >= 0");
     int poison = 0;
     if (const char *why = poison_from_env(poison)) return kl_err.fail(KL_EINVAL, why);
+    RefreshOptions refresh_opt;
+    if (const char *why = refresh_parse_options(refresh_opt, [](const char *knob) -> const char * { return getenv(knob); }))
+        return kl_err.fail(KL_EINVAL, why);
     if (!device_present()) return kl_err.fail(KL_ENODEV, "no HIP device");
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
+        return kl_err.fail(KL_ENODEV, "no HIP device");
     kl_ctx *c = new kl_ctx;
+    c->refresh_opt = refresh_opt;
+    c->num_cus = std::max(1, prop.multiProcessorCount);
     c->G = max_graphs;
     c->N = max_scans;
     c->M = max_edges;
@@ -267,6 +284,7 @@ int kl_create(kl_ctx **out, const kt_laser *laser, const kl_params *params, int 
     m.alloc(c->d_adj, sizeof(int2) * G * 2 * M);
     m.alloc(c->d_ends, sizeof(int2) * G * M);
     m.alloc(c->edit.d_info, sizeof(unsigned long long) * 2);
+    m.alloc(c->refresh.d_info, sizeof(unsigned long long) * 2);
     m.alloc(d.ref, sizeof(double2) * G * N);
     m.alloc(d.res, sizeof(kl_result) * Q);
     m.alloc(d.queries, sizeof(kl_query) * Q);
@@ -294,7 +312,7 @@ int kl_create(kl_ctx **out, const kt_laser *laser, const kl_params *params, int 
     hipStream_t s = c->order.stream;
     if ((e = hipMemsetAsync(c->d_hdr, 0, sizeof(KlHdr) * G, s)) != hipSuccess ||
         (e = hipMemsetAsync(d.emit_info, 0, sizeof(int) * 2, s)) != hipSuccess ||
-        (e = c->edit.reset_async(s)) != hipSuccess ||
+        (e = c->edit.reset_async(s)) != hipSuccess || (e = c->refresh.reset_async(s)) != hipSuccess ||
         (e = hipMemcpyAsync(d.res, r0.data(), sizeof(kl_result) * Q, hipMemcpyHostToDevice, s)) != hipSuccess ||
         (e = hipStreamSynchronize(s)) != hipSuccess || (e = hipEventRecord(c->order.ev_last, s)) != hipSuccess) {
         kl_destroy(c);
@@ -442,6 +460,35 @@ int kl_get_reference(kl_ctx *c, int g, int first, int count, double *out)
     if ((rc = c->order.wait_last(kl_err)) != KL_OK) return rc;
     S2D_CHK(kl_err, KL_EHIP, hipMemcpy(out, c->dev.ref + (size_t)g * c->N + first, sizeof(double2) * count, hipMemcpyDeviceToHost));
     return KL_OK;
+}
+
+int kl_refresh_device(kl_ctx *c, int n_rows, const kl_refresh_row *d_rows, const double *d_pool_ranges,
+                      const double *d_pool_poses, int pool_scans, kl_refresh_span *d_resolved_out, void *hip_stream)
+{
+    if (!c) return kl_err.fail(KL_EINVAL, "ctx is NULL");
+    if (n_rows < 0 || pool_scans < 0) return kl_err.fail(KL_EINVAL, "negative count");
+    if (n_rows > KL_REFRESH_MAX_ROWS) return kl_err.fail(KL_ERANGE, "more than KL_REFRESH_MAX_ROWS (4096) rows");
+    if (n_rows == 0) return KL_OK;
+    if (!d_rows || !d_pool_ranges || !d_pool_poses) return kl_err.fail(KL_EINVAL, "NULL argument");
+    StreamCall call(c->order, kl_err, hip_stream);
+    int rc = upload_dirty(c);  // an open row reads its graph's scan count from the device header
+    if (rc != KL_OK) return rc;
+    c->refresh.bump();
+    if ((rc = call.begin()) != KL_OK) return rc;
+    // the host knows no row, so the launch is sized by what the rows can name at most
+    const int grid = refresh_grid(c->refresh_opt, c->num_cus, refresh_bound(n_rows, c->N));
+    const KlRefresh r{d_rows, d_pool_ranges, d_pool_poses, (int2 *)d_resolved_out, c->refresh.d_info,
+                      n_rows, pool_scans, c->G, c->refresh.seq};
+    KL_LAUNCH(L_REFRESH, kl_refresh_kernel, dim3((unsigned)grid), dim3(KL_THREADS), 0, call.s, c->dev, r);
+    return call.done();
+}
+
+int kl_get_refresh_info(kl_ctx *c, int *n_refused, int *first_status)
+{
+    if (!c) return kl_err.fail(KL_EINVAL, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(c->order.mu);
+    const int rc = c->order.wait_last(kl_err);
+    return rc != KL_OK ? rc : c->refresh.read_and_reset(kl_err, n_refused, first_status);
 }
 
 int kl_search_device(kl_ctx *c, int count, const kl_query *d_queries, void *hip_stream)

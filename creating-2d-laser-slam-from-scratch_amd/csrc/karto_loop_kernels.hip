@@ -6,6 +6,8 @@
 //                        points of 1024 beams at a time are computed by all lanes into LDS; then one lane of wave 0
 //                        adds the x components and one lane of wave 1 the y components in beam order, one at a time
 //                        -- the reference's own order (a tree sum rounds differently); an invalid reading adds +0.0.
+//   kl_refresh_kernel    the same value for the scans named by rows of device memory: one launch of a host-known size,
+//                        a prefix sum of the rows' counts in every workgroup's LDS, one wave per scan.
 //   kl_search_kernel     one workgroup per query.  All lanes: the squared distances and, per scan, four threshold
 //                        bits.  Wave 0 and wave 1: the two breadth-first traversals (link and loop distance), each in
 //                        queue-prefix batches of up to 64 vertices with wave-level operations only, no workgroup
@@ -177,6 +179,126 @@ kl_reference_kernel(KlDev D, int g, int first, const double *__restrict__ ranges
             out.y = py;
         }
         D.ref[(size_t)g * D.max_scans + first + b] = out;
+    }
+}
+
+// =================================================================================================
+// kl_refresh_kernel: kl_reference_kernel's result for the scans that rows of device memory name
+// =================================================================================================
+// Row i names scans [first, first + count) of its graph, read from pool slots [pool_first, pool_first + count); count
+// < 0 stands for "through the graph's last scan" of the device header.  The host knows none of the counts, so the
+// launch has a fixed size (scan_refresh_plan.h) and every workgroup builds the same plan: the rows' resolved counts
+// and their exclusive prefix sum in LDS.  Scan s of that list belongs to the row found by bisection, and the waves of
+// the whole grid take the scans s = wave, wave + waves, ... -- one wave per scan, with no workgroup barrier after the
+// plan.  A wave computes 64 points at a time into its own slice of LDS; then lane 0 adds the x components and lane 1
+// the y components in beam order, in one loop, as kl_reference_kernel's two lanes do.  Workgroup 0 alone reports:
+// d_resolved_out and the refused rows.
+struct KlRefresh {
+    const kl_refresh_row *rows;
+    const double *ranges, *poses;  // [pool_scans][n_readings], [pool_scans][3]
+    int2 *resolved;                // [n_rows] or NULL
+    unsigned long long *info;      // ge_refuse's two words
+    int n_rows, pool_scans, max_graphs;
+    unsigned seq;
+};
+
+// the row's count as it is applied, 0 for a skipped or refused row; *status != KL_OK for a refused one
+__device__ inline int kl_refresh_resolve(const KlDev &D, const KlRefresh &R, const kl_refresh_row &r, int *status)
+{
+    *status = KL_OK;
+    if (r.graph < 0) return 0;
+    if (r.graph >= R.max_graphs || r.first < 0) {
+        *status = KL_EINVAL;
+        return 0;
+    }
+    const int count = r.count >= 0 ? r.count : max(D.hdr[r.graph].n_scans - r.first, 0);
+    if (r.first > D.max_scans - count) {
+        *status = KL_ERANGE;  // scans beyond the context's max_scans
+        return 0;
+    }
+    if (count > 0 && (r.pool_first < 0 || r.pool_first > R.pool_scans - count)) {
+        *status = KL_ERANGE;  // a slot outside the pool
+        return 0;
+    }
+    return count;
+}
+
+__global__ void __launch_bounds__(KL_THREADS) kl_refresh_kernel(KlDev D, KlRefresh R)
+{
+    __shared__ int s_off[KL_REFRESH_MAX_ROWS + 1];
+    __shared__ int s_sw[KL_WAVES];
+    __shared__ double s_pt[KL_WAVES][2][64];  // a wave's points: x components, y components
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = D.n_readings;
+    for (int i = tid; i < R.n_rows; i += KL_THREADS) {
+        const kl_refresh_row r = R.rows[i];
+        int status;
+        const int count = kl_refresh_resolve(D, R, r, &status);
+        s_off[i] = count;
+        if (blockIdx.x == 0) {
+            if (status != KL_OK) ge_refuse(R.info, R.seq, i, status);
+            if (R.resolved) R.resolved[i] = status == KL_OK && r.graph >= 0 ? make_int2(r.pool_first, count) : make_int2(0, 0);
+        }
+    }
+    __syncthreads();
+    const int total = ge_exscan_array(s_off, R.n_rows, s_sw);  // ends with a barrier: the last one
+
+    double *sx = s_pt[wave][0], *sy = s_pt[wave][1];
+    for (int s = blockIdx.x * KL_WAVES + wave; s < total; s += gridDim.x * KL_WAVES) {
+        // the last row whose offset is <= s: rows without scans share their successor's offset and are passed over
+        int lo = 0, hi = R.n_rows - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (s_off[mid] <= s) lo = mid;
+            else hi = mid - 1;
+        }
+        const kl_refresh_row r = R.rows[lo];
+        const int j = s - s_off[lo];
+        const size_t slot = (size_t)r.pool_first + j;
+        const double *raw = R.ranges + slot * n;
+        const double px = R.poses[3 * slot], py = R.poses[3 * slot + 1], ph = R.poses[3 * slot + 2];
+        double sum = 0.0;  // lane 0: x; lane 1: y
+        int cnt = 0;
+        if (D.use_barycenter) {
+            for (int c0 = 0; c0 < n; c0 += 64) {
+                const int cn = min(64, n - c0), i = c0 + lane;
+                bool ok = false;
+                double x = 0.0, y = 0.0;
+                if (lane < cn) {
+                    const double rr = raw[i];
+                    ok = rr >= D.minimum_range && rr <= D.range_threshold;  // math::InRange
+                    if (ok) {
+                        const double angle = ph + D.minimum_angle + (double)(unsigned)i * D.angular_resolution;
+                        x = px + (rr * sdm_cos(angle));
+                        y = py + (rr * sdm_sin(angle));
+                    }
+                }
+                cnt += __popcll(__ballot(ok));
+                sx[lane] = x;
+                sy[lane] = y;
+                kl_wave_sync();
+                // +0.0 for an invalid reading, as in kl_reference_kernel: the sum's bits are the branching loop's
+                if (lane < 2) {
+                    const double *p = s_pt[wave][lane];
+#pragma unroll 8
+                    for (int k = 0; k < cn; ++k) sum = sum + p[k];
+                }
+                kl_wave_sync();
+            }
+        }
+        const double sum_y = __shfl(sum, 1, 64);
+        if (lane == 0) {
+            double2 out;
+            if (cnt > 0) {
+                const double np = (double)cnt;
+                out.x = sum / np;
+                out.y = sum_y / np;
+            } else {
+                out.x = px;
+                out.y = py;
+            }
+            D.ref[(size_t)r.graph * D.max_scans + r.first + j] = out;
+        }
     }
 }
 

@@ -35,6 +35,7 @@ struct spa_ctx {
     std::vector<char> dirty;          // per graph: edited since the last upload
     std::vector<int> n_fixed;         // per graph: SysSPA2d::nFixed, or SPA_FIXED_FROM_PARAMS
     DeviceEditEpoch edit;  // device edits: which host copies are behind
+    DeviceEditEpoch rows;  // the row-indexed compute and export: their refusals' words and call numbers only
     int *d_ids = nullptr;
     SpaDev dev{};
     SpaHdr *d_hdr = nullptr;
@@ -164,6 +165,18 @@ int check_params(const spa_params *p)
     return SPA_OK;
 }
 
+// doSPA, one workgroup per graph: graphs [g_first, g_first + count), or those the `count` rows of graph_of name
+void launch_solve(spa_ctx *c, int count, int g_first, const int *graph_of, const SpaRows &rows, const spa_params *p,
+                  StreamCall &call)
+{
+    if (p->solver == SPA_SOLVER_CHOLESKY)
+        hipLaunchKernelGGL(spa_solve_kernel<SPA_SOLVER_CHOLESKY>, dim3((unsigned)count), dim3(SPA_THREADS), 0, call.s,
+                           c->dev, g_first, graph_of, rows, *p);
+    else
+        hipLaunchKernelGGL(spa_solve_kernel<SPA_SOLVER_PCG>, dim3((unsigned)count), dim3(SPA_THREADS), 0, call.s, c->dev,
+                           g_first, graph_of, rows, *p);
+}
+
 int run(spa_ctx *c, int g_first, int count, const spa_params *p, StreamCall &call)
 {
     int rc = check_params(p);
@@ -174,14 +187,22 @@ int run(spa_ctx *c, int g_first, int count, const spa_params *p, StreamCall &cal
         if (c->dirty[g] && (rc = upload_graph(c, g)) != SPA_OK) return rc;
     // order after the context's previous device work, whichever stream it ran on (DESIGN.md "Streams")
     if ((rc = call.begin()) != SPA_OK) return rc;
-    if (p->solver == SPA_SOLVER_CHOLESKY)
-        hipLaunchKernelGGL(spa_solve_kernel<SPA_SOLVER_CHOLESKY>, dim3((unsigned)count), dim3(SPA_THREADS), 0, call.s,
-                           c->dev, g_first, *p);
-    else
-        hipLaunchKernelGGL(spa_solve_kernel<SPA_SOLVER_PCG>, dim3((unsigned)count), dim3(SPA_THREADS), 0, call.s, c->dev,
-                           g_first, *p);
+    launch_solve(c, count, g_first, nullptr, SpaRows{}, p, call);
     return end_launch(call);
 }
+
+// before a call whose graphs are rows of device memory: any graph may be named, so every pending host edit goes up
+// (the only wait); the call gets the next number of the refusals' order
+int begin_rows(spa_ctx *c, StreamCall &call)
+{
+    int rc;
+    for (int g = 0; g < c->G; ++g)
+        if (c->dirty[g] && (rc = upload_graph(c, g)) != SPA_OK) return rc;
+    c->rows.bump();
+    return call.begin();
+}
+
+SpaRows rows_args(spa_ctx *c) { return SpaRows{c->rows.d_info, c->G, c->rows.seq}; }
 
 }  // namespace
 
@@ -239,6 +260,7 @@ int spa_create_ex(spa_ctx **out, int max_graphs, int max_nodes, int max_constrai
     m.alloc(c->dev.poses, sizeof(double) * G * N * 3);
     m.alloc(c->d_ids, sizeof(int) * G * N);
     m.alloc(c->edit.d_info, sizeof(unsigned long long) * 2);
+    m.alloc(c->rows.d_info, sizeof(unsigned long long) * 2);
     m.alloc(c->d_con_nd, sizeof(int2) * G * M);
     m.alloc(c->d_con_mean, sizeof(double) * G * M * 3);
     m.alloc(c->d_con_prec, sizeof(double) * G * M * 9);
@@ -277,6 +299,7 @@ int spa_create_ex(spa_ctx **out, int max_graphs, int max_nodes, int max_constrai
     if ((e = hipMemcpy(c->dev.stats, st.data(), sizeof(spa_stats) * G, hipMemcpyHostToDevice)) != hipSuccess ||
         (e = hipMemset(c->dev.poses, 0, sizeof(double) * G * N * 3)) != hipSuccess ||
         (e = c->edit.reset_async(c->order.stream)) != hipSuccess ||
+        (e = c->rows.reset_async(c->order.stream)) != hipSuccess ||
         (e = hipEventRecord(c->order.ev_last, c->order.stream)) != hipSuccess) {
         spa_destroy(c);
         return spa_err.fail(SPA_EHIP, "initialising the context", e);
@@ -414,6 +437,43 @@ int spa_compute(spa_ctx *c, int g_first, int count, const spa_params *params)
     if (rc != SPA_OK) return rc;
     S2D_CHK(spa_err, SPA_EHIP, hipStreamSynchronize(c->order.stream));
     return SPA_OK;
+}
+
+int spa_compute_rows_device(spa_ctx *c, int n_rows, const int *d_graph, const spa_params *params, void *hip_stream)
+{
+    if (!c) return spa_err.fail(SPA_EINVAL, "ctx is NULL");
+    int rc = check_params(params);
+    if (rc != SPA_OK) return rc;
+    if (n_rows < 0) return spa_err.fail(SPA_EINVAL, "negative count");
+    if (n_rows == 0) return SPA_OK;
+    if (!d_graph) return spa_err.fail(SPA_EINVAL, "d_graph is NULL");
+    StreamCall call(c->order, spa_err, hip_stream);
+    if ((rc = begin_rows(c, call)) != SPA_OK) return rc;
+    launch_solve(c, n_rows, 0, d_graph, rows_args(c), params, call);
+    return end_launch(call);
+}
+
+int spa_export_poses_device(spa_ctx *c, int n_rows, const int *d_graph, const int *d_pool_offset, double *d_pool_poses,
+                            int pool_scans, void *hip_stream)
+{
+    if (!c) return spa_err.fail(SPA_EINVAL, "ctx is NULL");
+    if (n_rows < 0 || pool_scans < 0) return spa_err.fail(SPA_EINVAL, "negative count");
+    if (n_rows == 0) return SPA_OK;
+    if (!d_graph || !d_pool_offset || !d_pool_poses) return spa_err.fail(SPA_EINVAL, "NULL argument");
+    StreamCall call(c->order, spa_err, hip_stream);
+    int rc = begin_rows(c, call);
+    if (rc != SPA_OK) return rc;
+    hipLaunchKernelGGL(spa_export_kernel, dim3((unsigned)n_rows), dim3(GE_THREADS), 0, call.s, c->dev, rows_args(c), c->d_ids,
+                       d_graph, d_pool_offset, (unsigned long long *)d_pool_poses, pool_scans);
+    return end_launch(call);
+}
+
+int spa_get_rows_info(spa_ctx *c, int *n_refused, int *first_status)
+{
+    if (!c) return spa_err.fail(SPA_EINVAL, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(c->order.mu);
+    const int rc = c->order.wait_last(spa_err);
+    return rc != SPA_OK ? rc : c->rows.read_and_reset(spa_err, n_refused, first_status);
 }
 
 int spa_get_nodes(spa_ctx *c, int g, int *ids_out, double *poses_out)

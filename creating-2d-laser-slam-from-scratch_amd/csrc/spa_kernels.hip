@@ -65,6 +65,14 @@ struct SpaDev {
     spa_stats *stats;         // [G]
 };
 
+// what the kernels that take their graphs from rows of device memory need besides: the refusals' two words
+// (ge_refuse) and the call's number
+struct SpaRows {
+    unsigned long long *info;
+    int max_graphs;
+    unsigned seq;
+};
+
 __host__ __device__ inline size_t spa_scratch_doubles(int max_nodes, int max_cons)
 {
     return (size_t)max_nodes * SPA_NODE_DOUBLES + (size_t)max_cons * SPA_CONS_DOUBLES;
@@ -354,8 +362,12 @@ __device__ inline bool spa_chol_solve(int nfree, const int *first, const int *la
     return true;
 }
 
+// graph_of NULL: workgroup b computes graph g_first + b.  Otherwise it computes graph graph_of[b] (rows of device
+// memory, spa_compute_rows_device) unless the row names no graph or an earlier row names the same one
+// (graph_edit_device.h's leader rule): such a workgroup leaves before it touches anything, all its lanes alike.
 template <int SOLVER>
-__global__ __launch_bounds__(SPA_THREADS) void spa_solve_kernel(SpaDev D, int g_first, spa_params P)
+__global__ __launch_bounds__(SPA_THREADS) void spa_solve_kernel(SpaDev D, int g_first, const int *__restrict__ graph_of,
+                                                                 SpaRows R, spa_params P)
 {
     __shared__ double red[SPA_THREADS];
     __shared__ int bc[5];
@@ -364,7 +376,14 @@ __global__ __launch_bounds__(SPA_THREADS) void spa_solve_kernel(SpaDev D, int g_
     __shared__ int iscan[CHOL ? SPA_THREADS : 1];
     __shared__ double ljj[CHOL ? 6 : 1];
     const int t = threadIdx.x;
-    const int g = g_first + blockIdx.x;
+    int g = g_first + blockIdx.x;
+    if (graph_of) {
+        g = graph_of[blockIdx.x];
+        static_assert(SPA_THREADS == GE_THREADS, "ge_is_leader strides by GE_THREADS");
+        const bool lead = ge_is_leader(graph_of, sizeof(int), blockIdx.x, g);
+        if (g >= R.max_graphs && t == 0) ge_refuse(R.info, R.seq, blockIdx.x, SPA_EINVAL);
+        if (g < 0 || g >= R.max_graphs || !lead) return;
+    }
     const size_t N = (size_t)D.max_nodes, M = (size_t)D.max_cons;
 
     if (t == 0) {
@@ -1004,6 +1023,47 @@ spa_edit_constraints_kernel(SpaEdit E, int count, const spa_con_row *__restrict_
     const int m = s_m;
     if (m == m0) return;
     spa_edit_rebuild(E, g, n, m, spa_edit_smem);
+}
+
+// =================================================================================================
+// spa_export_kernel: the loop of MapperGraph::CorrectPoses (Mapper.cpp:1404-1411) for the graphs rows name
+// =================================================================================================
+// One workgroup per row.  For the nodes k = 0 .. n - 1 of graph g in node order, pool[offset[g] + id[k]] = pose[k], the
+// three doubles moved as 64-bit words.  Ids that increase strictly (Karto's: a scan's id is its index) name every
+// slot once, so all lanes copy; otherwise lane 0 copies in node order and a later node with an id wins.  An id < 0
+// or a slot outside [0, pool_scans) is skipped and counted.
+__global__ void __launch_bounds__(GE_THREADS)
+spa_export_kernel(SpaDev D, SpaRows R, const int *__restrict__ ids, const int *__restrict__ graph_of,
+                  const int *__restrict__ pool_offset, unsigned long long *__restrict__ pool, int pool_scans)
+{
+    const int t = threadIdx.x, row = blockIdx.x;
+    const int g = graph_of[row];
+    if (g < 0) return;
+    if (g >= R.max_graphs) {
+        if (t == 0) ge_refuse(R.info, R.seq, row, SPA_EINVAL);
+        return;
+    }
+    const size_t N = (size_t)D.max_nodes;
+    const int n = min(max(D.hdr[g].n_nodes, 0), D.max_nodes);
+    const int *id = ids + g * N;
+    const unsigned long long *src = (const unsigned long long *)(D.poses + g * N * 3);
+    const long long off = pool_offset[g];
+    int ordered = 1;
+    for (int k = t; k + 1 < n; k += GE_THREADS) ordered &= id[k] < id[k + 1];
+    ordered = __syncthreads_and(ordered);
+    const auto copy = [&](int k) {
+        const long long slot = off + id[k];
+        if (id[k] < 0 || slot < 0 || slot >= pool_scans) {
+            ge_refuse(R.info, R.seq, row, SPA_ERANGE);
+            return;
+        }
+        for (int q = 0; q < 3; ++q) pool[3 * slot + q] = src[3 * (size_t)k + q];
+    };
+    if (ordered) {
+        for (int k = t; k < n; k += GE_THREADS) copy(k);
+    } else if (t == 0) {
+        for (int k = 0; k < n; ++k) copy(k);
+    }
 }
 
 }  // namespace s2d

@@ -1,4 +1,4 @@
-// stage_runtime.h -- the host runtime the Karto-family contexts share (kt_, kg_, spa_, kl_, ke_, kp_, kd_): status
+// stage_runtime.h -- the host runtime the Karto-family contexts share (kt_, kg_, spa_, kl_, ke_, kp_, kd_, kc_): status
 // codes, the module's error text, stream ordering between calls (DESIGN.md "Streams"), creation helpers, the timing
 // entry points and the device side of the edit epoch.  Host only.  The part above the __HIPCC__ line names no HIP
 // symbol and compiles as plain C++17 (tests/cpp/stage_runtime_check.cpp, with EditEpoch of karto_graph_mirror.h).
@@ -9,7 +9,7 @@
 
 namespace s2d {
 
-// The status codes of all seven public headers; each capi file asserts that its own XX_* equal them.
+// The status codes of all eight public headers; each capi file asserts that its own XX_* equal them.
 enum : int { S2D_OK = 0, S2D_EINVAL = -1, S2D_EHIP = -2, S2D_ENOMEM = -3, S2D_ENODEV = -4, S2D_ERANGE = -5 };
 #define S2D_ASSERT_STATUS_CODES(XX)                                                                          \
     static_assert(XX##_OK == s2d::S2D_OK && XX##_EINVAL == s2d::S2D_EINVAL && XX##_EHIP == s2d::S2D_EHIP &&   \

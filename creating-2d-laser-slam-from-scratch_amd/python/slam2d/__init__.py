@@ -4,6 +4,7 @@ grid path, PL-ICP, the Karto matcher, occupancy grid, pose-graph optimiser, loop
 Import is cheap; the HIP library is loaded on first use (slam2d._lib.lib()).
 """
 from ._lib import LIB_PATH, Slam2dError, build, lib  # noqa: F401
+from .karto_correct import PoseCorrection  # noqa: F401
 from .karto_edit import GraphEdits  # noqa: F401
 from .karto_grid import OccupancyGridBuilder  # noqa: F401
 from .karto_link import LinkStage  # noqa: F401
@@ -13,4 +14,4 @@ from .spa import SpaFleet, SpaSolver  # noqa: F401
 from .undistort import LidarUndistortion, UndistortFleet  # noqa: F401
 
 __all__ = ["LIB_PATH", "Slam2dError", "build", "lib", "LidarUndistortion", "UndistortFleet", "OccupancyGridBuilder", "SpaFleet",
-           "SpaSolver", "LoopSearchFleet", "LinkStage", "ProcessStage", "GraphEdits"]
+           "SpaSolver", "LoopSearchFleet", "LinkStage", "ProcessStage", "GraphEdits", "PoseCorrection"]

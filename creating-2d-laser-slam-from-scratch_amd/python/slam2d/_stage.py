@@ -1,5 +1,5 @@
 """What the wrappers of the Karto-family contexts share (karto.py, karto_grid.py, spa.py, karto_loop.py, karto_link.py,
-karto_process.py, karto_edit.py): the error check, the context's lifetime, the kernel timing calls and the ctypes
+karto_process.py, karto_edit.py, karto_correct.py): the error check, the context's lifetime, the kernel timing calls and the ctypes
 helpers.  A subclass names its C prefix (`_PREFIX = "kl"`), sets `self.L` and `self.h`, and mirrors its entry points.
 """
 from __future__ import annotations

@@ -58,7 +58,10 @@ def _declare(L):
     L.kt_set_scans.argtypes = [vp, i, i, vp, vp]
     L.kt_set_scans_device.argtypes = [vp, i, i, vp, vp, vp]
     L.kt_pool_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i)]
-    L.kt_match_scan.argtypes = [vp, vp, vp, i, vp, vp, i, i, C.POINTER(KtResult)]
+    L.kt_refresh_device.argtypes = [vp, i, vp, vp, vp, i, vp]
+    L.kt_get_refresh_info.argtypes = [vp, C.POINTER(i), C.POINTER(i)]
+    L.kt_get_prepared.argtypes = [vp, i, C.POINTER(i), vp, vp, vp, vp]
+    L.kt_match_scan.argtypes =[vp, vp, vp, i, vp, vp, i, i, C.POINTER(KtResult)]
     L.kt_match_batch_device.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp]
     L.kt_window_exchange_words.restype = C.c_size_t
     L.kt_window_exchange_words.argtypes = [vp]
@@ -144,6 +147,31 @@ class ScanMatcher(TimedStage):
         r, p, m = C.c_void_p(), C.c_void_p(), C.c_int()
         self._check(self.L.kt_pool_device(self.h, C.byref(r), C.byref(p), C.byref(m)), "kt_pool_device")
         return int(r.value or 0), int(p.value or 0), int(m.value)
+
+    def refresh_device(self, n_rows: int, d_rows: int, d_pool_ranges: int, d_pool_poses: int, pool_scans: int,
+                       hip_stream: int = 0):
+        """kt_refresh_device: prepare the pool slots the `n_rows` rows {first slot, count} at device address d_rows
+        name, from row s of the given pool arrays (the context's own: in place)."""
+        self._check(self.L.kt_refresh_device(self.h, int(n_rows), _dp(d_rows), _dp(d_pool_ranges), _dp(d_pool_poses),
+                                             int(pool_scans), _dp(hip_stream)), "kt_refresh_device")
+
+    def refresh_info(self):
+        """(rows kt_refresh_device refused since the last call, status of the first); waits."""
+        n, st = C.c_int(0), C.c_int(0)
+        self._check(self.L.kt_get_refresh_info(self.h, C.byref(n), C.byref(st)), "kt_get_refresh_info")
+        return n.value, st.value
+
+    def prepared(self, slot: int) -> dict:
+        """Diagnostic (kt_get_prepared): pool slot `slot`'s point readings pts [npts, 2], local points loc [npts, 2],
+        bad [npts] and reset events evt [npts, 2]."""
+        n = self.laser.n_readings
+        k = C.c_int(0)
+        pts, loc = np.zeros((n, 2), np.float64), np.zeros((n, 2), np.float64)
+        bad, evt = np.zeros(n, np.uint8), np.zeros((n, 2), np.int32)
+        self._check(self.L.kt_get_prepared(self.h, int(slot), C.byref(k), _hp(pts), _hp(loc), _hp(bad), _hp(evt)),
+                    "kt_get_prepared")
+        k = k.value
+        return {"npts": k, "pts": pts[:k].copy(), "loc": loc[:k].copy(), "bad": bad[:k].copy(), "evt": evt[:k].copy()}
 
     def match_batch_device(self, count: int, d_query: int, d_base_begin: int, d_base_index: int, d_results: int,
                            doPenalize: bool = True, doRefineMatch: bool = True, hip_stream: int = 0):

@@ -45,6 +45,9 @@ CLOSEST_ITEM_DTYPE = np.dtype([(k, np.int32) for k in ("graph", "scan", "begin",
 CLOSEST_DTYPE = np.dtype([(k, np.int32) for k in ("closest", "linked")])
 SOURCE_DTYPE = np.dtype([(k, np.int32) for k in ("slot", "chain")])
 EDGE_ROW_DTYPE = np.dtype([(k, np.int32) for k in ("graph", "source", "target", "pad_")])
+REFRESH_ROW_DTYPE = np.dtype([(k, np.int32) for k in ("graph", "first", "count", "pool_first")])
+REFRESH_SPAN_DTYPE = np.dtype([(k, np.int32) for k in ("pool_first", "count")])
+KL_REFRESH_MAX_ROWS = 4096
 
 
 class KlEdgeRow(C.Structure):
@@ -72,6 +75,8 @@ def _declare(L):
     L.kl_set_scans.argtypes = [vp, i, i, i, vp, vp]
     L.kl_set_scans_device.argtypes = [vp, i, i, i, vp, vp, vp]
     L.kl_get_reference.argtypes = [vp, i, i, i, vp]
+    L.kl_refresh_device.argtypes = [vp, i, vp, vp, vp, i, vp, vp]
+    L.kl_get_refresh_info.argtypes = [vp, P(i), P(i)]
     L.kl_search.argtypes = [vp, i, vp]
     L.kl_search_device.argtypes = [vp, i, vp, vp]
     L.kl_get_result.argtypes = [vp, i, P(KlResult)]
@@ -169,6 +174,19 @@ class LoopSearchFleet(TimedStage):
         out = np.zeros((count, 2), np.float64)
         self._check(self.L.kl_get_reference(self.h, g, int(first), int(count), _hp(out)), "kl_get_reference")
         return out
+
+    def refresh_device(self, n_rows: int, d_rows: int, d_pool_ranges: int, d_pool_poses: int, pool_scans: int,
+                       d_resolved: int = 0, hip_stream: int = 0):
+        """kl_refresh_device: `n_rows` kl_refresh_row rows (REFRESH_ROW_DTYPE) at device address d_rows; d_resolved
+        gets REFRESH_SPAN_DTYPE rows."""
+        self._check(self.L.kl_refresh_device(self.h, int(n_rows), _dp(d_rows), _dp(d_pool_ranges), _dp(d_pool_poses),
+                                             int(pool_scans), _dp(d_resolved), _dp(hip_stream)), "kl_refresh_device")
+
+    def refresh_info(self):
+        """(rows kl_refresh_device refused since the last call, status of the first); waits."""
+        n, st = C.c_int(0), C.c_int(0)
+        self._check(self.L.kl_get_refresh_info(self.h, C.byref(n), C.byref(st)), "kl_get_refresh_info")
+        return n.value, st.value
 
     # ------------------------------------------------------------------------------------------------ the search
     def search(self, rows):

@@ -77,6 +77,9 @@ def _declare(L):
     L.spa_get_counts.argtypes = [vp, i, P(i), P(i)]
     L.spa_compute.argtypes = [vp, i, i, P(SpaParams)]
     L.spa_compute_device.argtypes = [vp, i, i, P(SpaParams), vp]
+    L.spa_compute_rows_device.argtypes = [vp, i, vp, P(SpaParams), vp]
+    L.spa_export_poses_device.argtypes = [vp, i, vp, vp, vp, i, vp]
+    L.spa_get_rows_info.argtypes = [vp, P(i), P(i)]
     L.spa_get_nodes.argtypes = [vp, i, vp, vp]
     L.spa_device_poses.argtypes = [vp, i, P(vp), P(i)]
     L.spa_get_stats.argtypes = [vp, i, P(SpaStats)]
@@ -266,6 +269,25 @@ class SpaFleet(Stage):
         p = params if params is not None else default_params()
         self._check(self.L.spa_compute_device(self.h, int(g_first), int(count), C.byref(p),
                                               C.c_void_p(hip_stream or None)), "spa_compute_device")
+
+    def compute_rows_device(self, n_rows: int, d_graph: int, params: SpaParams | None = None, hip_stream: int = 0):
+        """spa_compute_rows_device: doSPA on the graphs the `n_rows` ints at device address d_graph name."""
+        p = params if params is not None else default_params()
+        self._check(self.L.spa_compute_rows_device(self.h, int(n_rows), _dp(d_graph), C.byref(p), _dp(hip_stream)),
+                    "spa_compute_rows_device")
+
+    def export_poses_device(self, n_rows: int, d_graph: int, d_pool_offset: int, d_pool_poses: int, pool_scans: int,
+                            hip_stream: int = 0):
+        """spa_export_poses_device: CorrectPoses' loop, pool[offset[g] + id] = pose for the named graphs' nodes."""
+        self._check(self.L.spa_export_poses_device(self.h, int(n_rows), _dp(d_graph), _dp(d_pool_offset),
+                                                   _dp(d_pool_poses), int(pool_scans), _dp(hip_stream)),
+                    "spa_export_poses_device")
+
+    def rows_info(self):
+        """(rows or nodes the two row-indexed calls refused since the last call, status of the first); waits."""
+        n, st = C.c_int(0), C.c_int(0)
+        self._check(self.L.spa_get_rows_info(self.h, C.byref(n), C.byref(st)), "spa_get_rows_info")
+        return n.value, st.value
 
     def get_nodes(self, g: int):
         """(ids [n], poses [n, 3]) in node order."""

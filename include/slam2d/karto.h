@@ -104,6 +104,26 @@ int kt_set_scans_device(kt_ctx *ctx, int first, int count, const double *d_range
  * any output may be NULL. */
 int kt_pool_device(kt_ctx *ctx, const double **d_ranges, const double **d_poses, int *max_scans);
 
+/* kt_set_scans_device for pool slots that ROWS OF DEVICE MEMORY name: row i = {first slot, count} (two ints, the
+ * layout of HIP's int2; kl_refresh_device of karto_loop.h writes such rows), n_rows <= KT_REFRESH_MAX_ROWS.  Pool
+ * slot s is prepared from row s of d_pool_ranges double[pool_scans][n_readings] and d_pool_poses
+ * double[pool_scans][3].  When these are the context's own arrays (kt_pool_device) the work is in place; another
+ * array's readings / poses are stored into the pool as well.  One launch on hip_stream (NULL: the context's), with
+ * no host synchronisation and no copy call.  count <= 0 skips a row; a row outside [0, min(max_scans, pool_scans)]
+ * is refused (KT_EINVAL), written nowhere and counted.  The other slots are untouched.
+ * SLAM2D_REFRESH_WG (read once, at kt_create; one whole decimal integer, anything else is refused there with
+ * KT_EINVAL): > 0 caps the launch at that many workgroups. */
+#define KT_REFRESH_MAX_ROWS 4096
+int kt_refresh_device(kt_ctx *ctx, int n_rows, const void *d_rows, const double *d_pool_ranges,
+                      const double *d_pool_poses, int pool_scans, void *hip_stream);
+/* Rows kt_refresh_device refused since the last call of this function, and the status of the first of them in
+ * (call, row) order (KT_OK: none).  Waits for the device. */
+int kt_get_refresh_info(kt_ctx *ctx, int *n_refused, int *first_status);
+/* Diagnostic: what pool slot `slot` holds prepared.  Waits for the device.  *npts point readings; pts and loc
+ * double[npts][2], bad unsigned char[npts], evt int[npts][2], each given room for n_readings entries; any output may
+ * be NULL. */
+int kt_get_prepared(kt_ctx *ctx, int slot, int *npts, double *pts, double *loc, unsigned char *bad, int *evt);
+
 /* One MatchScan (host arrays, synchronous; uses pool slots 0 .. n_base). */
 int kt_match_scan(kt_ctx *ctx, const double *query_ranges, const double query_pose[3], int n_base,
                   const double *base_ranges, const double *base_poses, int do_penalize, int do_refine,

@@ -8,6 +8,8 @@
  *   kl_add_vertex          MapperGraph::AddVertex (the scan's state id is the vertex count before the call)
  *   kl_add_edge            MapperGraph::AddEdge                                              Mapper.cpp:1075-1101
  *   kl_set_scans[_device]  LocalizedRangeScan::Update, the barycentre only                   Karto.h:5374-5416
+ *   kl_refresh_device      the same for scans named by rows of device memory (after SetSensorPose at Mapper.cpp:1032,
+ *                          :2044, and for every scan of a graph in CorrectPoses, Mapper.cpp:1397-1414)
  *   kl_search[_device]     FindNearLinkedScans (BreadthFirstTraversal::Traverse with NearScanVisitor)
  *                                                                       Mapper.cpp:1278-1286, Mapper.h:568-637
  *                          FindPossibleLoopClosure, every call of TryCloseLoop's while loop  Mapper.cpp:1333-1394
@@ -168,6 +170,36 @@ int kl_set_scans_device(kl_ctx *ctx, int g, int first, int count, const double *
                         void *hip_stream);
 /* out double[count][2] */
 int kl_get_reference(kl_ctx *ctx, int g, int first, int count, double *out);
+
+/* The same refresh for scans that ROWS OF DEVICE MEMORY name, so that a fleet round needs no count on the host: row i
+ * recomputes the reference position of scans [first, first + count) of `graph`, scan first + j from row pool_first + j
+ * of d_pool_ranges double[pool_scans][n_readings] and d_pool_poses double[pool_scans][3].  The value written is
+ * kl_set_scans_device's, bit for bit; scans named by no row keep theirs.  One launch, stream-ordered, with no host
+ * synchronisation and no copy -- unless a graph has pending HOST edits, which are uploaded first (the only case in
+ * which the call waits).
+ *
+ * count < 0: through the graph's last scan as the DEVICE header has it (n_scans - first, or 0 when that is negative).
+ * graph < 0: the row is skipped.  A row is refused, writes nothing and is counted (kl_get_refresh_info) for a graph
+ * >= max_graphs or first < 0 (KL_EINVAL), and for scans beyond max_scans or a pool slot outside [0, pool_scans)
+ * (KL_ERANGE); an explicit count is bounded by max_scans only, as kl_set_scans_device's is.  d_resolved_out[i] (may
+ * be NULL) is {pool_first, the count applied}, {0, 0} for a skipped or refused row.  Two rows that name the same scan
+ * must name the same pool slot for it.  More than KL_REFRESH_MAX_ROWS rows are refused with KL_ERANGE at the call.
+ *
+ * SLAM2D_REFRESH_WG (read once, at kl_create; one whole decimal integer, anything else is refused there with
+ * KL_EINVAL): > 0 caps the launch at that many workgroups. */
+#define KL_REFRESH_MAX_ROWS 4096
+typedef struct kl_refresh_row {
+    int graph, first, count, pool_first;
+} kl_refresh_row;
+/* d_resolved_out's element; the layout of HIP's int2 (this header stays plain C) */
+typedef struct kl_refresh_span {
+    int pool_first, count;
+} kl_refresh_span;
+int kl_refresh_device(kl_ctx *ctx, int n_rows, const kl_refresh_row *d_rows, const double *d_pool_ranges,
+                      const double *d_pool_poses, int pool_scans, kl_refresh_span *d_resolved_out, void *hip_stream);
+/* Rows kl_refresh_device refused since the last call of this function, and the status of the first of them in
+ * (call, row) order (KL_OK: none).  Waits. */
+int kl_get_refresh_info(kl_ctx *ctx, int *n_refused, int *first_status);
 
 /* `count` (<= max_queries) queries, one workgroup each, one launch, no host synchronisation; query i's results go
  * to slot i and stay on the device until the next search.  Only graphs edited since their last search cost more:

@@ -162,6 +162,29 @@ int spa_envelope_blocks(spa_ctx *ctx, int g, int n_fixed, long long *blocks);
 int spa_compute(spa_ctx *ctx, int g_first, int count, const spa_params *params);
 int spa_compute_device(spa_ctx *ctx, int g_first, int count, const spa_params *params, void *hip_stream);
 
+/* GRAPHS NAMED BY ROWS OF DEVICE MEMORY, so that the host needs to know neither which graphs are computed nor their
+ * node counts.  Both calls enqueue one launch on hip_stream (NULL: the context's) and return, with no host
+ * synchronisation and no copy -- unless a graph (any graph: a row may name it) has pending HOST edits, which are
+ * uploaded first (the only case in which they wait).
+ *
+ * spa_compute_rows_device: workgroup i runs doSPA on graph d_graph[i] exactly as spa_compute_device would.  A row is
+ * passed over when its entry is negative or when an earlier row names the same graph; an entry >= max_graphs is
+ * refused (SPA_EINVAL, counted).  Poses and spa_stats of graphs that are not computed are untouched.
+ *
+ * spa_export_poses_device: the loop of MapperGraph::CorrectPoses (Mapper.cpp:1404-1411).  For row i's graph g =
+ * d_graph[i] (negative: passed over; >= max_graphs: refused, SPA_EINVAL) and its nodes k = 0 .. n_nodes - 1 in node
+ * order, d_pool_poses[d_pool_offset[g] + id[k]] = pose[k], the three doubles copied as bits; d_pool_offset is
+ * int[max_graphs], d_pool_poses double[pool_scans][3].  A later node with the same id overwrites an earlier one.  A
+ * node whose id is < 0 or whose slot lies outside [0, pool_scans) is skipped and counted (SPA_ERANGE, under its
+ * row).  n_nodes is the DEVICE header's.
+ *
+ * spa_get_rows_info: rows (export: nodes) these two calls refused since the last call of this function, and the
+ * status of the first of them in (call, row) order (SPA_OK: none).  Waits. */
+int spa_compute_rows_device(spa_ctx *ctx, int n_rows, const int *d_graph, const spa_params *params, void *hip_stream);
+int spa_export_poses_device(spa_ctx *ctx, int n_rows, const int *d_graph, const int *d_pool_offset,
+                            double *d_pool_poses, int pool_scans, void *hip_stream);
+int spa_get_rows_info(spa_ctx *ctx, int *n_refused, int *first_status);
+
 /* ids_out int[n], poses_out double[n][3] in node order; either may be NULL.  Waits for the last compute. */
 int spa_get_nodes(spa_ctx *ctx, int g, int *ids_out, double *poses_out);
 /* The same poses on the device, double[n][3]: the d_poses layout kg_build_device and kt_set_scans_device
