@@ -12,28 +12,14 @@
 #include <vector>
 
 #include "../../include/slam2d/gmapping.h"
+#include "stage_runtime.h"
 #include "gmapping_kernels.hip"
 
 using namespace s2d;
 
 namespace {
-thread_local std::string gm_err;
-
-int gfail(int code, const char *what, hipError_t e = hipSuccess)
-{
-    gm_err = what;
-    if (e != hipSuccess) {
-        gm_err += ": ";
-        gm_err += hipGetErrorString(e);
-    }
-    return code;
-}
-
-#define GCHK(expr)                                             \
-    do {                                                       \
-        hipError_t _e = (expr);                                \
-        if (_e != hipSuccess) return gfail(GM_EHIP, #expr, _e); \
-    } while (0)
+thread_local StageError gm_err;
+S2D_ASSERT_COMMON_CODES(GM);
 }  // namespace
 
 struct gm_ctx {
@@ -53,10 +39,8 @@ struct gm_ctx {
     float *d_ranges = nullptr;
     int8_t *d_occ = nullptr;
     hipStream_t stream = nullptr;
-    bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_used, ev_free;
-    double acc_ms = 0;
-    int64_t acc_n = 0;
+    DeviceBuffers mem;
+    KernelTimer timer;  // one index: the span of gm_score_kernel + gm_compute_kernel
 };
 
 namespace {
@@ -72,8 +56,8 @@ int reset_state(gm_ctx *c)
         memset(&s, 0, sizeof(s));
         s.tx0 = 1; s.ty0 = 1; s.tx1 = 0; s.ty1 = 0;  // empty box: a fresh map
     }
-    GCHK(hipMemcpy(c->d_state, h.data(), sizeof(GmState) * c->P, hipMemcpyHostToDevice));
-    GCHK(hipMemset(c->d_stamps, 0, sizeof(int) * (size_t)c->geom.ntiles * c->P));
+    S2D_CHK(gm_err, GM_EHIP, hipMemcpy(c->d_state, h.data(), sizeof(GmState) * c->P, hipMemcpyHostToDevice));
+    S2D_CHK(gm_err, GM_EHIP, hipMemset(c->d_stamps, 0, sizeof(int) * (size_t)c->geom.ntiles * c->P));
     return GM_OK;
 }
 
@@ -81,27 +65,13 @@ int launch(gm_ctx *c, int begin, int count, const double *d_poses, const float *
            hipStream_t s)
 {
     if (count <= 0) return GM_OK;
-    std::pair<hipEvent_t, hipEvent_t> ev{};
-    if (c->timing) {
-        if (!c->ev_free.empty()) {
-            ev = c->ev_free.back();
-            c->ev_free.pop_back();
-        } else {
-            GCHK(hipEventCreate(&ev.first));
-            GCHK(hipEventCreate(&ev.second));
-        }
-        GCHK(hipEventRecord(ev.first, s));
-    }
+    S2D_CHK(gm_err, GM_EHIP, c->timer.begin(s));
     hipLaunchKernelGGL(gm_score_kernel, dim3(count), dim3(GM_THREADS), 0, s, c->geom, d_poses, d_ranges, n, c->d_cos,
                        c->d_sin, c->d_maps, c->d_stamps, c->d_state, d_scores, begin, c->d_rays, c->d_hitxy, c->d_hits);
-    GCHK(hipGetLastError());
+    S2D_CHK(gm_err, GM_EHIP, hipGetLastError());
     hipLaunchKernelGGL(gm_compute_kernel, dim3(count * c->parts), dim3(GM_THREADS), gm_shmem(n), s, c->geom, d_poses,
                        n, c->d_rays, c->d_hitxy, c->d_maps, c->d_stamps, c->d_hits, c->d_state, begin, count, c->parts);
-    GCHK(hipGetLastError());
-    if (c->timing) {
-        GCHK(hipEventRecord(ev.second, s));
-        c->ev_used.push_back(ev);
-    }
+    S2D_CHK(gm_err, GM_EHIP, c->timer.end(s, 0));  // the launch's error, timing or not
     return GM_OK;
 }
 }  // namespace
@@ -114,12 +84,11 @@ const char *gm_last_error(void) { return gm_err.c_str(); }
 int gm_create(gm_ctx **out, int num_particles, int max_beams, double xmin, double ymin, double xmax, double ymax,
               double delta, double max_range, double max_urange)
 {
-    if (!out) return gfail(GM_EINVAL, "out is NULL");
+    if (!out) return gm_err.fail(GM_EINVAL, "out is NULL");
     *out = nullptr;
     if (num_particles < 1 || max_beams < 1 || max_beams > 8192 || !(delta > 0) || !(xmax > xmin) || !(ymax > ymin))
-        return gfail(GM_EINVAL, "invalid particles / beams / map bounds");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return gfail(GM_ENODEV, "no HIP device");
+        return gm_err.fail(GM_EINVAL, "invalid particles / beams / map bounds");
+    if (!device_present()) return gm_err.fail(GM_ENODEV, "no HIP device");
     gm_ctx *c = new gm_ctx;
     c->P = num_particles;
     c->max_beams = max_beams;
@@ -139,7 +108,7 @@ int gm_create(gm_ctx **out, int num_particles, int max_beams, double xmin, doubl
     g.max_beams = max_beams;
     if (g.sx < 32 || g.sy < 32 || g.sx > 16384 || g.sy > 16384 || !(max_range / delta < 16384.0)) {
         delete c;
-        return gfail(GM_EINVAL, "map must be 32..16384 cells per side and max_range/delta < 16384");
+        return gm_err.fail(GM_EINVAL, "map must be 32..16384 cells per side and max_range/delta < 16384");
     }
     g.tiles_x = (g.sx + GM_TILE - 1) / GM_TILE;
     g.tiles_y = (g.sy + GM_TILE_H - 1) / GM_TILE_H;
@@ -148,21 +117,22 @@ int gm_create(gm_ctx **out, int num_particles, int max_beams, double xmin, doubl
     hipError_t e;
     if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamDefault)) != hipSuccess) {
         delete c;
-        return gfail(GM_EHIP, "hipStreamCreate", e);
+        return gm_err.fail(GM_EHIP, "hipStreamCreate", e);
     }
-    if ((e = hipMalloc(&c->d_maps, sizeof(unsigned) * g.particle_words * (size_t)c->P)) != hipSuccess ||
-        (e = hipMalloc(&c->d_stamps, sizeof(int) * (size_t)g.ntiles * c->P)) != hipSuccess ||
-        (e = hipMalloc(&c->d_rays, sizeof(unsigned) * (size_t)max_beams * c->P)) != hipSuccess ||
-        (e = hipMalloc(&c->d_hitxy, sizeof(float2) * (size_t)max_beams * c->P)) != hipSuccess ||
-        (e = hipMalloc(&c->d_hits, sizeof(GmHitCell) * (size_t)max_beams * c->P)) != hipSuccess ||
-        (e = hipMalloc(&c->d_state, sizeof(GmState) * c->P)) != hipSuccess ||
-        (e = hipMalloc(&c->d_cos, sizeof(double) * max_beams)) != hipSuccess ||
-        (e = hipMalloc(&c->d_sin, sizeof(double) * max_beams)) != hipSuccess ||
-        (e = hipMalloc(&c->d_poses, sizeof(double) * 4 * c->P)) != hipSuccess ||
-        (e = hipMalloc(&c->d_ranges, sizeof(float) * max_beams)) != hipSuccess ||
-        (e = hipMalloc(&c->d_occ, (size_t)g.sx * g.sy)) != hipSuccess) {
+    c->mem.alloc(c->d_maps, sizeof(unsigned) * g.particle_words * (size_t)c->P);
+    c->mem.alloc(c->d_stamps, sizeof(int) * (size_t)g.ntiles * c->P);
+    c->mem.alloc(c->d_rays, sizeof(unsigned) * (size_t)max_beams * c->P);
+    c->mem.alloc(c->d_hitxy, sizeof(float2) * (size_t)max_beams * c->P);
+    c->mem.alloc(c->d_hits, sizeof(GmHitCell) * (size_t)max_beams * c->P);
+    c->mem.alloc(c->d_state, sizeof(GmState) * c->P);
+    c->mem.alloc(c->d_cos, sizeof(double) * max_beams);
+    c->mem.alloc(c->d_sin, sizeof(double) * max_beams);
+    c->mem.alloc(c->d_poses, sizeof(double) * 4 * c->P);
+    c->mem.alloc(c->d_ranges, sizeof(float) * max_beams);
+    c->mem.alloc(c->d_occ, (size_t)g.sx * g.sy);
+    if ((e = c->mem.error) != hipSuccess) {
         gm_destroy(c);
-        return gfail(GM_ENOMEM, "hipMalloc", e);
+        return gm_err.fail(GM_ENOMEM, "hipMalloc", e);
     }
     int rc = reset_state(c);
     if (rc != GM_OK) {
@@ -177,19 +147,8 @@ int gm_destroy(gm_ctx *c)
 {
     if (!c) return GM_OK;
     if (c->stream) hipStreamSynchronize(c->stream);
-    hipFree(c->d_maps);
-    hipFree(c->d_rays);
-    hipFree(c->d_hitxy);
-    hipFree(c->d_stamps);
-    hipFree(c->d_hits);
-    hipFree(c->d_state);
-    hipFree(c->d_cos);
-    hipFree(c->d_sin);
-    hipFree(c->d_poses);
-    hipFree(c->d_ranges);
-    hipFree(c->d_occ);
-    for (auto &p : c->ev_used) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
-    for (auto &p : c->ev_free) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
+    c->mem.free_all();
+    c->timer.destroy();
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
     return GM_OK;
@@ -197,31 +156,31 @@ int gm_destroy(gm_ctx *c)
 
 int gm_reset(gm_ctx *c)
 {
-    if (!c) return gfail(GM_EINVAL, "ctx is NULL");
-    GCHK(hipStreamSynchronize(c->stream));
-    GCHK(hipDeviceSynchronize());
+    if (!c) return gm_err.fail(GM_EINVAL, "ctx is NULL");
+    S2D_CHK(gm_err, GM_EHIP, hipStreamSynchronize(c->stream));
+    S2D_CHK(gm_err, GM_EHIP, hipDeviceSynchronize());
     return reset_state(c);
 }
 
 int gm_set_beams(gm_ctx *c, const double *a_cos, const double *a_sin, int n)
 {
-    if (!c || !a_cos || !a_sin || n < 1 || n > c->max_beams) return gfail(GM_EINVAL, "invalid beam cache");
-    GCHK(hipMemcpy(c->d_cos, a_cos, sizeof(double) * n, hipMemcpyHostToDevice));
-    GCHK(hipMemcpy(c->d_sin, a_sin, sizeof(double) * n, hipMemcpyHostToDevice));
+    if (!c || !a_cos || !a_sin || n < 1 || n > c->max_beams) return gm_err.fail(GM_EINVAL, "invalid beam cache");
+    S2D_CHK(gm_err, GM_EHIP, hipMemcpy(c->d_cos, a_cos, sizeof(double) * n, hipMemcpyHostToDevice));
+    S2D_CHK(gm_err, GM_EHIP, hipMemcpy(c->d_sin, a_sin, sizeof(double) * n, hipMemcpyHostToDevice));
     c->n_beams = n;
     return GM_OK;
 }
 
 int gm_set_occ_thresh(gm_ctx *c, double t)
 {
-    if (!c) return gfail(GM_EINVAL, "ctx is NULL");
+    if (!c) return gm_err.fail(GM_EINVAL, "ctx is NULL");
     c->geom.occ_thresh = t;
     return GM_OK;
 }
 
 int gm_get_map_size(gm_ctx *c, int *sx, int *sy)
 {
-    if (!c) return gfail(GM_EINVAL, "ctx is NULL");
+    if (!c) return gm_err.fail(GM_EINVAL, "ctx is NULL");
     if (sx) *sx = c->geom.sx;
     if (sy) *sy = c->geom.sy;
     return GM_OK;
@@ -229,22 +188,22 @@ int gm_get_map_size(gm_ctx *c, int *sx, int *sy)
 
 int gm_compute_maps(gm_ctx *c, const double *poses, const float *ranges, int n)
 {
-    if (!c || !poses || (!ranges && n > 0)) return gfail(GM_EINVAL, "NULL argument");
-    if (n < 0 || n > c->n_beams) return gfail(GM_EINVAL, "n exceeds the beam cache (gm_set_beams)");
-    GCHK(hipMemcpyAsync(c->d_poses, poses, sizeof(double) * 4 * c->P, hipMemcpyHostToDevice, c->stream));
-    if (n > 0) GCHK(hipMemcpyAsync(c->d_ranges, ranges, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
+    if (!c || !poses || (!ranges && n > 0)) return gm_err.fail(GM_EINVAL, "NULL argument");
+    if (n < 0 || n > c->n_beams) return gm_err.fail(GM_EINVAL, "n exceeds the beam cache (gm_set_beams)");
+    S2D_CHK(gm_err, GM_EHIP, hipMemcpyAsync(c->d_poses, poses, sizeof(double) * 4 * c->P, hipMemcpyHostToDevice, c->stream));
+    if (n > 0) S2D_CHK(gm_err, GM_EHIP, hipMemcpyAsync(c->d_ranges, ranges, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
     int rc = launch(c, 0, c->P, c->d_poses, c->d_ranges, n, nullptr, c->stream);
     if (rc != GM_OK) return rc;
-    GCHK(hipStreamSynchronize(c->stream));
+    S2D_CHK(gm_err, GM_EHIP, hipStreamSynchronize(c->stream));
     return GM_OK;
 }
 
 int gm_compute_maps_device(gm_ctx *c, int begin, int count, const double *d_poses, const float *d_ranges, int n,
                            int32_t *d_scores_out, void *hip_stream)
 {
-    if (!c || !d_poses || (!d_ranges && n > 0)) return gfail(GM_EINVAL, "NULL argument");
-    if (begin < 0 || count < 0 || begin + count > c->P) return gfail(GM_EINVAL, "particle range out of bounds");
-    if (n < 0 || n > c->n_beams) return gfail(GM_EINVAL, "n exceeds the beam cache (gm_set_beams)");
+    if (!c || !d_poses || (!d_ranges && n > 0)) return gm_err.fail(GM_EINVAL, "NULL argument");
+    if (begin < 0 || count < 0 || begin + count > c->P) return gm_err.fail(GM_EINVAL, "particle range out of bounds");
+    if (n < 0 || n > c->n_beams) return gm_err.fail(GM_EINVAL, "n exceeds the beam cache (gm_set_beams)");
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
     return launch(c, begin, count, d_poses, d_ranges, n, d_scores_out, s);
 }
@@ -252,47 +211,45 @@ int gm_compute_maps_device(gm_ctx *c, int begin, int count, const double *d_pose
 int gm_normalize_weights_device(gm_ctx *c, void *nccl_comm, const int32_t *d_scores, int count, double *d_weights_out,
                                 double *d_sums_out, void *hip_stream)
 {
-    if (!c || !d_sums_out || (count > 0 && !d_scores)) return gfail(GM_EINVAL, "NULL argument");
-    if (count < 0) return gfail(GM_EINVAL, "count < 0");
+    if (!c || !d_sums_out || (count > 0 && !d_scores)) return gm_err.fail(GM_EINVAL, "NULL argument");
+    if (count < 0) return gm_err.fail(GM_EINVAL, "count < 0");
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
     hipLaunchKernelGGL(gm_weight_sums_kernel, dim3(1), dim3(GM_THREADS), 0, s, d_scores, count, d_sums_out);
-    GCHK(hipGetLastError());
+    S2D_CHK(gm_err, GM_EHIP, hipGetLastError());
     if (nccl_comm) {
         // the one exchange of the sharded particle set: 2 doubles, summed over the ranks (RCCL over xGMI)
         const ncclResult_t r = ncclAllReduce(d_sums_out, d_sums_out, 2, ncclDouble, ncclSum, (ncclComm_t)nccl_comm, s);
-        if (r != ncclSuccess) {
-            gm_err = std::string("ncclAllReduce: ") + ncclGetErrorString(r);
-            return GM_EHIP;
-        }
+        if (r != ncclSuccess)
+            return gm_err.fail(GM_EHIP, (std::string("ncclAllReduce: ") + ncclGetErrorString(r)).c_str());
     }
     if (d_weights_out && count > 0) {
         hipLaunchKernelGGL(gm_weights_kernel, dim3((count + 255) / 256), dim3(256), 0, s, d_scores, count, d_sums_out,
                            d_weights_out);
-        GCHK(hipGetLastError());
+        S2D_CHK(gm_err, GM_EHIP, hipGetLastError());
     }
     return GM_OK;
 }
 
 int gm_get_particle_map(gm_ctx *c, int p, int32_t *n_out, int32_t *visits_out, float *acc_out)
 {
-    if (!c || p < 0 || p >= c->P) return gfail(GM_EINVAL, "invalid particle");
-    GCHK(hipDeviceSynchronize());
+    if (!c || p < 0 || p >= c->P) return gm_err.fail(GM_EINVAL, "invalid particle");
+    S2D_CHK(gm_err, GM_EHIP, hipDeviceSynchronize());
     const GmGeom &g = c->geom;
     GmState st;
-    GCHK(hipMemcpy(&st, c->d_state + p, sizeof(GmState), hipMemcpyDeviceToHost));
+    S2D_CHK(gm_err, GM_EHIP, hipMemcpy(&st, c->d_state + p, sizeof(GmState), hipMemcpyDeviceToHost));
     const size_t cells = (size_t)g.sx * g.sy;
     if (n_out) memset(n_out, 0, sizeof(int32_t) * cells);
     if (visits_out) memset(visits_out, 0, sizeof(int32_t) * cells);
     if (acc_out) memset(acc_out, 0, sizeof(float) * 2 * cells);
     if (st.step == 0 || st.tx1 < st.tx0) return GM_OK;
     std::vector<int> stamps(g.ntiles);
-    GCHK(hipMemcpy(stamps.data(), c->d_stamps + (size_t)p * g.ntiles, sizeof(int) * g.ntiles, hipMemcpyDeviceToHost));
+    S2D_CHK(gm_err, GM_EHIP, hipMemcpy(stamps.data(), c->d_stamps + (size_t)p * g.ntiles, sizeof(int) * g.ntiles, hipMemcpyDeviceToHost));
     std::vector<unsigned> tile(GM_TILE_BLOCK_WORDS);
     const unsigned *pm = c->d_maps + (size_t)p * g.particle_words;
     for (int ty = st.ty0; ty <= st.ty1; ++ty)
         for (int tx = st.tx0; tx <= st.tx1; ++tx) {
             if (stamps[ty * g.tiles_x + tx] != st.step) continue;  // not written this step: fresh
-            GCHK(hipMemcpy(tile.data(), pm + (size_t)(ty * g.tiles_x + tx) * GM_TILE_BLOCK_WORDS,
+            S2D_CHK(gm_err, GM_EHIP, hipMemcpy(tile.data(), pm + (size_t)(ty * g.tiles_x + tx) * GM_TILE_BLOCK_WORDS,
                            sizeof(unsigned) * GM_TILE_BLOCK_WORDS, hipMemcpyDeviceToHost));
             for (int r = 0; r < GM_TILE_H; ++r) {
                 const int y = ty * GM_TILE_H + r;
@@ -309,7 +266,7 @@ int gm_get_particle_map(gm_ctx *c, int p, int32_t *n_out, int32_t *visits_out, f
         }
     if (acc_out && st.hit_cells > 0) {
         std::vector<GmHitCell> hits(st.hit_cells);
-        GCHK(hipMemcpy(hits.data(), c->d_hits + (size_t)p * c->max_beams, sizeof(GmHitCell) * st.hit_cells,
+        S2D_CHK(gm_err, GM_EHIP, hipMemcpy(hits.data(), c->d_hits + (size_t)p * c->max_beams, sizeof(GmHitCell) * st.hit_cells,
                        hipMemcpyDeviceToHost));
         for (const auto &h : hits) {
             if (h.cell < 0) continue;  // a beam that is not its cell's first hit (or no hit)
@@ -322,24 +279,24 @@ int gm_get_particle_map(gm_ctx *c, int p, int32_t *n_out, int32_t *visits_out, f
 
 int gm_publish(gm_ctx *c, int p, int8_t *occ_out)
 {
-    if (!c || !occ_out || p < 0 || p >= c->P) return gfail(GM_EINVAL, "invalid argument");
-    GCHK(hipDeviceSynchronize());
+    if (!c || !occ_out || p < 0 || p >= c->P) return gm_err.fail(GM_EINVAL, "invalid argument");
+    S2D_CHK(gm_err, GM_EHIP, hipDeviceSynchronize());
     GmState st;
-    GCHK(hipMemcpy(&st, c->d_state + p, sizeof(GmState), hipMemcpyDeviceToHost));
+    S2D_CHK(gm_err, GM_EHIP, hipMemcpy(&st, c->d_state + p, sizeof(GmState), hipMemcpyDeviceToHost));
     hipLaunchKernelGGL(gm_publish_kernel, dim3(1024), dim3(256), 0, c->stream, c->d_maps + (size_t)p * c->geom.particle_words,
                        c->d_stamps + (size_t)p * c->geom.ntiles, c->geom, st.step, c->d_occ);
-    GCHK(hipGetLastError());
-    GCHK(hipMemcpyAsync(occ_out, c->d_occ, (size_t)c->geom.sx * c->geom.sy, hipMemcpyDeviceToHost, c->stream));
-    GCHK(hipStreamSynchronize(c->stream));
+    S2D_CHK(gm_err, GM_EHIP, hipGetLastError());
+    S2D_CHK(gm_err, GM_EHIP, hipMemcpyAsync(occ_out, c->d_occ, (size_t)c->geom.sx * c->geom.sy, hipMemcpyDeviceToHost, c->stream));
+    S2D_CHK(gm_err, GM_EHIP, hipStreamSynchronize(c->stream));
     return GM_OK;
 }
 
 int gm_get_scores(gm_ctx *c, int32_t *scores_out, int32_t *hits_out, int64_t *free_out)
 {
-    if (!c) return gfail(GM_EINVAL, "ctx is NULL");
-    GCHK(hipDeviceSynchronize());
+    if (!c) return gm_err.fail(GM_EINVAL, "ctx is NULL");
+    S2D_CHK(gm_err, GM_EHIP, hipDeviceSynchronize());
     std::vector<GmState> h(c->P);
-    GCHK(hipMemcpy(h.data(), c->d_state, sizeof(GmState) * c->P, hipMemcpyDeviceToHost));
+    S2D_CHK(gm_err, GM_EHIP, hipMemcpy(h.data(), c->d_state, sizeof(GmState) * c->P, hipMemcpyDeviceToHost));
     for (int p = 0; p < c->P; ++p) {
         if (scores_out) scores_out[p] = h[p].score;
         if (hits_out) hits_out[p] = h[p].hits;
@@ -350,30 +307,14 @@ int gm_get_scores(gm_ctx *c, int32_t *scores_out, int32_t *hits_out, int64_t *fr
 
 int gm_set_timing(gm_ctx *c, int enable)
 {
-    if (!c) return gfail(GM_EINVAL, "ctx is NULL");
-    c->timing = enable != 0;
-    return GM_OK;
+    if (!c) return gm_err.fail(GM_EINVAL, "ctx is NULL");
+    return set_timing(c->timer, enable);
 }
 
 int gm_get_kernel_times(gm_ctx *c, double *ms_out, int64_t *launches_out, int reset)
 {
-    if (!c) return gfail(GM_EINVAL, "ctx is NULL");
-    GCHK(hipDeviceSynchronize());
-    for (auto &p : c->ev_used) {
-        float ms = 0;
-        GCHK(hipEventElapsedTime(&ms, p.first, p.second));
-        c->acc_ms += ms;
-        c->acc_n += 1;
-        c->ev_free.push_back(p);
-    }
-    c->ev_used.clear();
-    if (ms_out) *ms_out = c->acc_ms;
-    if (launches_out) *launches_out = c->acc_n;
-    if (reset) {
-        c->acc_ms = 0;
-        c->acc_n = 0;
-    }
-    return GM_OK;
+    if (!c) return gm_err.fail(GM_EINVAL, "ctx is NULL");
+    return get_kernel_times(c->timer, gm_err, ms_out, launches_out, reset, 1);
 }
 
 }  // extern "C"

@@ -15,37 +15,17 @@
 #include <vector>
 
 #include "../../include/slam2d/hector.h"
+#include "stage_runtime.h"
 #include "hector_kernels.hip"
 
 using namespace s2d;
 
 namespace {
-thread_local std::string g_err;
+thread_local StageError hs_err;
+S2D_ASSERT_COMMON_CODES(HS);
 
-int fail(int code, const char *what, hipError_t e = hipSuccess)
-{
-    g_err = what;
-    if (e != hipSuccess) {
-        g_err += ": ";
-        g_err += hipGetErrorString(e);
-    }
-    return code;
-}
-
-#define LOCK(c) std::lock_guard<std::recursive_mutex> lock_(c->mu)
-
-#define HCHK(expr)                                          \
-    do {                                                    \
-        hipError_t _e = (expr);                             \
-        if (_e != hipSuccess) return fail(HS_EHIP, #expr, _e); \
-    } while (0)
-
-constexpr int NKERN = 3;
-
-struct EventPair {
-    hipEvent_t a, b;
-    int kernel;
-};
+enum { K_MATCH, K_BIN, K_UPDATE, K_NUM };  // hs_get_kernel_times; K_UPDATE: hs_update_kernel (default) or hs_tile_kernel
+static_assert(K_NUM <= KernelTimer::MAX_KERNELS, "the timer's accumulators");
 }  // namespace
 
 struct hs_ctx {
@@ -65,12 +45,13 @@ struct hs_ctx {
     float *d_out_cov = nullptr;
     int8_t *d_occ = nullptr;
     PoseLog plog{nullptr, 0, 0, nullptr};
-    hipStream_t stream = nullptr;
-    // timing
-    bool timing = false;
-    std::vector<EventPair> ev_used, ev_free;
-    double acc_ms[NKERN] = {0, 0, 0};
-    int64_t acc_n[NKERN] = {0, 0, 0};
+    // order.stream runs the host-pointer calls.  Every *_device call waits on its own stream for the context's
+    // previous device work, so the per-context scratch -- update lists, ingest buffers, queues -- is never used by
+    // two streams at once; order.mu serialises host calls on one context (e.g. a publish thread's hs_get_map
+    // against the spin thread's hs_update, hector_slam.cc:277 vs :201)
+    StreamOrder order;
+    DeviceBuffers mem;
+    KernelTimer timer;
     // binned grid update scratch
     unsigned *d_rays = nullptr;
     uint4 *d_segs = nullptr;
@@ -93,12 +74,6 @@ struct hs_ctx {
     // 256 = the 256-thread tree (hs_set_reduction_order; opt.reduce_order at hs_create)
     int reduce_order = 0;
     hipEvent_t ev_upd[MAX_PARTS] = {};
-    // the last device work of the context (every *_device call waits for it on its own stream, so the
-    // per-context scratch -- update lists, ingest buffers, queues -- is never used by two streams at once)
-    hipEvent_t ev_last = nullptr;
-    // serialises host calls on one context (e.g. a publish thread's hs_get_map against the spin
-    // thread's hs_update, hector_slam.cc:277 vs :201)
-    std::recursive_mutex mu;
     // scan ingest (hs_set_laser): unit vectors, geometry
     bool has_laser = false;
     IngestGeom ingest{};
@@ -190,14 +165,14 @@ StreamState initial_state()
 int reset_all(hs_ctx *c, bool full)
 {
     size_t nwords = c->cells_bytes / sizeof(float);
-    hipLaunchKernelGGL(hs_fill_cells_kernel, dim3(4096), dim3(256), 0, c->stream, c->d_cells, nwords,
+    hipLaunchKernelGGL(hs_fill_cells_kernel, dim3(4096), dim3(256), 0, c->order.stream, c->d_cells, nwords,
                        c->geom.stream_words);
-    HCHK(hipGetLastError());
+    S2D_CHK(hs_err, HS_EHIP, hipGetLastError());
     std::vector<StreamState> h(c->B, initial_state());
     if (!full) {
         std::vector<StreamState> old(c->B);
-        HCHK(hipMemcpyAsync(old.data(), c->d_state, sizeof(StreamState) * c->B, hipMemcpyDeviceToHost, c->stream));
-        HCHK(hipStreamSynchronize(c->stream));
+        S2D_CHK(hs_err, HS_EHIP, hipMemcpyAsync(old.data(), c->d_state, sizeof(StreamState) * c->B, hipMemcpyDeviceToHost, c->order.stream));
+        S2D_CHK(hs_err, HS_EHIP, hipStreamSynchronize(c->order.stream));
         for (int s = 0; s < c->B; ++s) {
             StreamState &o = old[s];
             o.last_upd_pose[0] = o.last_upd_pose[1] = o.last_upd_pose[2] = FLT_MAX;
@@ -211,36 +186,14 @@ int reset_all(hs_ctx *c, bool full)
             h[s] = o;
         }
     }
-    HCHK(hipMemcpyAsync(c->d_state, h.data(), sizeof(StreamState) * c->B, hipMemcpyHostToDevice, c->stream));
+    S2D_CHK(hs_err, HS_EHIP, hipMemcpyAsync(c->d_state, h.data(), sizeof(StreamState) * c->B, hipMemcpyHostToDevice, c->order.stream));
     for (int p = 0; p < MAX_PARTS; ++p)
         for (int i = 0; i < 2; ++i)
-            if (c->wl[p][i]) HCHK(hipMemsetAsync(c->wl[p][i], 0, sizeof(int) * 4, c->stream));
+            if (c->wl[p][i]) S2D_CHK(hs_err, HS_EHIP, hipMemsetAsync(c->wl[p][i], 0, sizeof(int) * 4, c->order.stream));
     for (int p = 0; p < MAX_PARTS; ++p) c->wl_parity[p] = 0;
     c->ord_steps = 0;  // every stream starts a new ordinal epoch
-    HCHK(hipStreamSynchronize(c->stream));
+    S2D_CHK(hs_err, HS_EHIP, hipStreamSynchronize(c->order.stream));
     return HS_OK;
-}
-
-EventPair *begin_timed(hs_ctx *c, int kernel, hipStream_t s)
-{
-    if (!c->timing) return nullptr;
-    EventPair p;
-    if (!c->ev_free.empty()) {
-        p = c->ev_free.back();
-        c->ev_free.pop_back();
-    } else {
-        if (hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) return nullptr;
-    }
-    p.kernel = kernel;
-    hipEventRecord(p.a, s);
-    c->ev_used.push_back(p);
-    return &c->ev_used.back();
-}
-
-void end_timed(hs_ctx *c, hipStream_t s)
-{
-    if (!c->timing || c->ev_used.empty()) return;
-    hipEventRecord(c->ev_used.back().b, s);
 }
 
 HsShape shape(const hs_ctx *c) { return HsShape{c->B, c->levels, c->max_points, c->sx, c->sy, c->ncu, c->big, c->ingest.n}; }
@@ -250,13 +203,13 @@ int launch_part(hs_ctx *c, int part, int begin, int count, const float2 *xy, int
                 const float2 *origo, const float *hints, int mode, float *out_pose, float *out_cov, hipStream_t s,
                 hipEvent_t wait_before_update = nullptr, const MatchIngest *mi = nullptr)
 {
-    if (part < 0 || part >= c->opt.nq) return fail(HS_EINVAL, "internal: part without a queue slot");
+    if (part < 0 || part >= c->opt.nq) return hs_err.fail(HS_EINVAL, "internal: part without a queue slot");
     const StepPlan plan = plan_step(c->opt, shape(c), c->reduce_order, count, mode);
     WorkQueue *wq = c->d_wq + part;
     // the single-kernel update consumes the match kernel's list of updating streams (wl[part][parity]: one
     // pair of lists per part)
     UpdList *wl_cur = plan.use_list ? c->wl[part][c->wl_parity[part]] : nullptr;
-    begin_timed(c, 0, s);
+    S2D_CHK(hs_err, HS_EHIP, c->timer.begin(s));
     const MatchIngest mik = mi ? *mi : MatchIngest{};
 #define S2D_MATCH_LAUNCH(SEQ, REGS, BIG)                                                                                 \
     hipLaunchKernelGGL((hs_match_kernel<SEQ, REGS, BIG>), dim3(count), dim3(MATCH_THREADS), 0, s, c->geom, c->d_cells,    \
@@ -269,10 +222,9 @@ int launch_part(hs_ctx *c, int part, int begin, int count, const float2 *xy, int
     else if (plan.regs) S2D_MATCH_LAUNCH(false, true, false);
     else S2D_MATCH_LAUNCH(false, false, false);
 #undef S2D_MATCH_LAUNCH
-    end_timed(c, s);
-    HCHK(hipGetLastError());
+    S2D_CHK(hs_err, HS_EHIP, c->timer.end(s, K_MATCH));  // the launch's error, timing or not
     if (mode == MODE_MATCH_ONLY) return HS_OK;
-    if (wait_before_update) HCHK(hipStreamWaitEvent(s, wait_before_update, 0));
+    if (wait_before_update) S2D_CHK(hs_err, HS_EHIP, hipStreamWaitEvent(s, wait_before_update, 0));
     // wl_next: the list the update clears for the next step's match (null lists: every stream of the batch, split
     // by geom.upd_parts)
     UpdList *wl_next = nullptr;
@@ -280,7 +232,7 @@ int launch_part(hs_ctx *c, int part, int begin, int count, const float2 *xy, int
 #define S2D_UPDATE_LAUNCH(KERNEL, THREADS)                                                                               \
     hipLaunchKernelGGL(KERNEL, dim3(plan.blocks), dim3(THREADS), plan.shmem, s, c->geom, c->d_cells, c->d_state, xy,      \
                        xy_stride, c->d_ixy, c->max_points, begin, count, c->max_points, wl_cur, wl_next, c->ncu)
-    begin_timed(c, plan.upd == UPD_BINNED ? 1 : 2, s);
+    S2D_CHK(hs_err, HS_EHIP, c->timer.begin(s));
     switch (plan.upd) {
     case UPD_BINNED: {
         uint4 *segs = c->d_segs + (size_t)part * c->seg_cap;
@@ -289,9 +241,8 @@ int launch_part(hs_ctx *c, int part, int begin, int count, const float2 *xy, int
         hipLaunchKernelGGL(hs_bin_kernel, dim3(count), dim3(BIN_THREADS), 0, s, c->geom, c->d_state, xy, xy_stride,
                            c->d_ixy, c->max_points, begin, c->max_points, c->d_rays, segs, items, wholes, wq, c->seg_cap,
                            c->item_cap);
-        end_timed(c, s);
-        HCHK(hipGetLastError());
-        begin_timed(c, 2, s);
+        S2D_CHK(hs_err, HS_EHIP, c->timer.end(s, K_BIN));
+        S2D_CHK(hs_err, HS_EHIP, c->timer.begin(s));
         hipLaunchKernelGGL(hs_tile_kernel, dim3(c->tile_grid), dim3(TILE_THREADS), 0, s, c->geom, c->d_cells, c->d_state,
                            c->d_rays, segs, items, wholes, wq, c->max_points);
         break;
@@ -301,8 +252,7 @@ int launch_part(hs_ctx *c, int part, int begin, int count, const float2 *xy, int
     case UPD_CLIP_LDS: S2D_UPDATE_LAUNCH((hs_update_kernel<0>), UPD_THREADS); break;
     }
 #undef S2D_UPDATE_LAUNCH
-    end_timed(c, s);
-    HCHK(hipGetLastError());
+    S2D_CHK(hs_err, HS_EHIP, c->timer.end(s, K_UPDATE));
     return HS_OK;
 }
 
@@ -318,9 +268,9 @@ int ord_sweep_if_due(hs_ctx *c, hipStream_t s)
     const int tiles = (int)(c->geom.cells_words / TILE_BLOCK_WORDS);
     hipLaunchKernelGGL(hs_ord_sweep_kernel, dim3(4096), dim3(256), 0, s, c->d_cells, c->d_state, c->geom.stream_words,
                        tiles, 0, c->B);
-    HCHK(hipGetLastError());
+    S2D_CHK(hs_err, HS_EHIP, hipGetLastError());
     hipLaunchKernelGGL(hs_ord_epoch_kernel, dim3((c->B + 255) / 256), dim3(256), 0, s, c->d_state, 0, c->B);
-    HCHK(hipGetLastError());
+    S2D_CHK(hs_err, HS_EHIP, hipGetLastError());
     c->ord_steps = 1;
     return HS_OK;
 }
@@ -334,14 +284,14 @@ int launch_step(hs_ctx *c, int begin, int count, const float2 *xy, int xy_stride
     const int parts = (mode == MODE_PROCESS && count >= 64 * c->opt.nparts) ? c->opt.nparts : 1;
     if (parts == 1)
         return launch_part(c, 0, begin, count, xy, xy_stride, n, origo, hints, mode, out_pose, out_cov, s, nullptr, mi);
-    HCHK(hipEventRecord(c->ev_start, s));
+    S2D_CHK(hs_err, HS_EHIP, hipEventRecord(c->ev_start, s));
     const int per = (count + parts - 1) / parts;
     for (int p = 0; p < parts; ++p) {
         const int off = p * per;
         const int cnt = count - off < per ? count - off : per;
         if (cnt <= 0) break;
         hipStream_t ps = c->pstream[p];
-        HCHK(hipStreamWaitEvent(ps, c->ev_start, 0));
+        S2D_CHK(hs_err, HS_EHIP, hipStreamWaitEvent(ps, c->ev_start, 0));
         MatchIngest pmi = mi ? *mi : MatchIngest{};
         if (mi) {
             pmi.ranges += (size_t)off * mi->rstride;
@@ -354,33 +304,20 @@ int launch_step(hs_ctx *c, int begin, int count, const float2 *xy, int xy_stride
                              out_pose ? out_pose + 3 * (size_t)off : nullptr, out_cov ? out_cov + 9 * (size_t)off : nullptr,
                              ps, nullptr, mi ? &pmi : nullptr);
         if (rc != HS_OK) return rc;
-        HCHK(hipEventRecord(c->ev_done[p], ps));
-        HCHK(hipStreamWaitEvent(s, c->ev_done[p], 0));
+        S2D_CHK(hs_err, HS_EHIP, hipEventRecord(c->ev_done[p], ps));
+        S2D_CHK(hs_err, HS_EHIP, hipStreamWaitEvent(s, c->ev_done[p], 0));
     }
     return HS_OK;
 }
 
 int check_stream(hs_ctx *c, int stream) { return (c && stream >= 0 && stream < c->B) ? HS_OK : HS_EINVAL; }
 
-// *_device calls may name any HIP stream: order each call after the context's previous device work
-// (enter) and publish its own (leave), so two calls never share the context's scratch concurrently
-int dev_enter(hs_ctx *c, hipStream_t s)
-{
-    HCHK(hipStreamWaitEvent(s, c->ev_last, 0));
-    return HS_OK;
-}
-int dev_leave(hs_ctx *c, hipStream_t s)
-{
-    HCHK(hipEventRecord(c->ev_last, s));
-    return HS_OK;
-}
-
 int launch_ingest(hs_ctx *c, int count, const float *d_ranges, int range_stride, float2 *d_xy, int xy_stride, int *d_n,
                   float2 *d_origo, hipStream_t s)
 {
     hipLaunchKernelGGL(hs_ingest_kernel, dim3(count), dim3(256), 0, s, c->ingest, c->d_cs, d_ranges, range_stride, d_xy,
                        xy_stride, d_n, d_origo);
-    HCHK(hipGetLastError());
+    S2D_CHK(hs_err, HS_EHIP, hipGetLastError());
     return HS_OK;
 }
 
@@ -402,12 +339,12 @@ int launch_ranges_step(hs_ctx *c, int begin, int count, const float *d_ranges, i
 // Stage one host scan into the single-stream buffers.
 int stage_scan(hs_ctx *c, const float *xy, int n, float ox, float oy, const float *hint)
 {
-    if (n < 0 || n > c->max_points || (n > 0 && !xy)) return fail(HS_EINVAL, "bad scan size / pointer");
-    if (n > 0) HCHK(hipMemcpyAsync(c->d_pts1, xy, sizeof(float2) * n, hipMemcpyHostToDevice, c->stream));
-    HCHK(hipMemcpyAsync(c->d_n1, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if (n < 0 || n > c->max_points || (n > 0 && !xy)) return hs_err.fail(HS_EINVAL, "bad scan size / pointer");
+    if (n > 0) S2D_CHK(hs_err, HS_EHIP, hipMemcpyAsync(c->d_pts1, xy, sizeof(float2) * n, hipMemcpyHostToDevice, c->order.stream));
+    S2D_CHK(hs_err, HS_EHIP, hipMemcpyAsync(c->d_n1, &n, sizeof(int), hipMemcpyHostToDevice, c->order.stream));
     float2 o = make_float2(ox, oy);
-    HCHK(hipMemcpyAsync(c->d_origo1, &o, sizeof(float2), hipMemcpyHostToDevice, c->stream));
-    if (hint) HCHK(hipMemcpyAsync(c->d_hint1, hint, sizeof(float) * 3, hipMemcpyHostToDevice, c->stream));
+    S2D_CHK(hs_err, HS_EHIP, hipMemcpyAsync(c->d_origo1, &o, sizeof(float2), hipMemcpyHostToDevice, c->order.stream));
+    if (hint) S2D_CHK(hs_err, HS_EHIP, hipMemcpyAsync(c->d_hint1, hint, sizeof(float) * 3, hipMemcpyHostToDevice, c->order.stream));
     return HS_OK;
 }
 
@@ -420,23 +357,22 @@ extern "C" {
 #endif
 const char *hs_version(void) { return "slam2d-mi355x hector 0.1 (gfx950) src " SLAM2D_SRC_HASH; }
 const char *hs_source_id(void) { return SLAM2D_SRC_HASH; }
-const char *hs_last_error(void) { return g_err.c_str(); }
+const char *hs_last_error(void) { return hs_err.c_str(); }
 
 int hs_create(hs_ctx **out, int num_streams, float map_resolution, int map_size_x, int map_size_y, float map_start_x,
               float map_start_y, int levels, int max_points)
 {
-    if (!out) return fail(HS_EINVAL, "out is NULL");
+    if (!out) return hs_err.fail(HS_EINVAL, "out is NULL");
     *out = nullptr;
     if (num_streams < 1 || levels < 1 || levels > HS_MAX_LEVELS || map_size_x < 2 || map_size_y < 2 ||
         map_size_x > 32768 || map_size_y > 32768 || max_points < 1 || max_points > 65535 || !(map_resolution > 0.0f))
-        return fail(HS_EINVAL, "invalid hs_create arguments");
+        return hs_err.fail(HS_EINVAL, "invalid hs_create arguments");
     if ((map_size_x >> (levels - 1)) < 2 || (map_size_y >> (levels - 1)) < 2)
-        return fail(HS_EINVAL, "map too small for the requested number of levels");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HS_ENODEV, "no HIP device");
+        return hs_err.fail(HS_EINVAL, "map too small for the requested number of levels");
+    if (!device_present()) return hs_err.fail(HS_ENODEV, "no HIP device");
     HsOptions opt;
     const char *refused = parse_options(opt, [](const char *knob) -> const char * { return getenv(knob); });
-    if (refused) return fail(HS_EINVAL, refused);
+    if (refused) return hs_err.fail(HS_EINVAL, refused);
     hs_ctx *c = new hs_ctx();
     c->opt = opt;
     c->reduce_order = opt.reduce_order;
@@ -455,25 +391,21 @@ int hs_create(hs_ctx **out, int num_streams, float map_resolution, int map_size_
     c->geom.min_ang = 0.13f * 1.0f;
     c->cells_bytes = sizeof(float) * c->geom.stream_words * (size_t)num_streams;
     hipError_t e;
-    // blocking streams (not hipStreamNonBlocking): work a caller queued on the legacy default stream
-    // (e.g. torch's default stream zeroing an output) is ordered before the context's own kernels
-    if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamDefault)) != hipSuccess) {
+    if ((e = c->order.create()) != hipSuccess) {
+        c->order.destroy();
         delete c;
-        return fail(HS_EHIP, "hipStreamCreate", e);
+        return hs_err.fail(HS_EHIP, "hipStreamCreate", e);
     }
-    if ((e = hipMalloc(&c->d_cells, c->cells_bytes)) != hipSuccess ||
-        (e = hipMalloc(&c->d_state, sizeof(StreamState) * num_streams)) != hipSuccess ||
-        (e = hipMalloc(&c->d_pts1, sizeof(float2) * max_points)) != hipSuccess ||
-        (e = hipMalloc(&c->d_n1, sizeof(int))) != hipSuccess ||
-        (e = hipMalloc(&c->d_origo1, sizeof(float2))) != hipSuccess ||
-        (e = hipMalloc(&c->d_hint1, sizeof(float) * 3)) != hipSuccess ||
-        (e = hipMalloc(&c->d_out_pose, sizeof(float) * 3 * num_streams)) != hipSuccess ||
-        (e = hipMalloc(&c->d_out_cov, sizeof(float) * 9 * num_streams)) != hipSuccess ||
-        (e = hipMalloc(&c->d_occ, (size_t)map_size_x * map_size_y)) != hipSuccess ||
-        (e = hipMalloc(&c->d_ixy, sizeof(float2) * (size_t)num_streams * max_points)) != hipSuccess) {
-        hs_destroy(c);
-        return fail(HS_ENOMEM, "hipMalloc", e);
-    }
+    c->mem.alloc(c->d_cells, c->cells_bytes);
+    c->mem.alloc(c->d_state, sizeof(StreamState) * num_streams);
+    c->mem.alloc(c->d_pts1, sizeof(float2) * max_points);
+    c->mem.alloc(c->d_n1, sizeof(int));
+    c->mem.alloc(c->d_origo1, sizeof(float2));
+    c->mem.alloc(c->d_hint1, sizeof(float) * 3);
+    c->mem.alloc(c->d_out_pose, sizeof(float) * 3 * num_streams);
+    c->mem.alloc(c->d_out_cov, sizeof(float) * 9 * num_streams);
+    c->mem.alloc(c->d_occ, (size_t)map_size_x * map_size_y);
+    c->mem.alloc(c->d_ixy, sizeof(float2) * (size_t)num_streams * max_points);
     {
         // grid-update queues: 6 segments per ray on average, 512 non-empty tiles per stream level
         const size_t sl = (size_t)num_streams * levels;
@@ -502,29 +434,25 @@ int hs_create(hs_ctx **out, int num_streams, float map_resolution, int map_size_
                 (e = hipEventCreateWithFlags(&c->ev_done[p], hipEventDisableTiming)) != hipSuccess ||
                 (e = hipEventCreateWithFlags(&c->ev_upd[p], hipEventDisableTiming)) != hipSuccess) {
                 hs_destroy(c);
-                return fail(HS_EHIP, "hipStreamCreate(part)", e);
+                return hs_err.fail(HS_EHIP, "hipStreamCreate(part)", e);
             }
         }
-        if ((e = hipEventCreateWithFlags(&c->ev_start, hipEventDisableTiming)) != hipSuccess ||
-            (e = hipEventCreateWithFlags(&c->ev_last, hipEventDisableTiming)) != hipSuccess) {
+        if ((e = hipEventCreateWithFlags(&c->ev_start, hipEventDisableTiming)) != hipSuccess) {
             hs_destroy(c);
-            return fail(HS_EHIP, "hipEventCreate", e);
+            return hs_err.fail(HS_EHIP, "hipEventCreate", e);
         }
     }
-    if ((e = hipMalloc(&c->d_rays, sizeof(unsigned) * (size_t)num_streams * levels * max_points)) != hipSuccess ||
-        (e = hipMalloc(&c->d_segs, sizeof(uint4) * (size_t)c->seg_cap * c->opt.nq)) != hipSuccess ||
-        (e = hipMalloc(&c->d_items, sizeof(WorkItem) * (size_t)c->item_cap * c->opt.nq)) != hipSuccess ||
-        (e = hipMalloc(&c->d_wholes, sizeof(WorkItem) * (size_t)num_streams * levels * c->opt.nq)) != hipSuccess ||
-        (e = hipMalloc(&c->d_wq, sizeof(WorkQueue) * c->opt.nq)) != hipSuccess) {
-        hs_destroy(c);
-        return fail(HS_ENOMEM, "hipMalloc", e);
-    }
+    c->mem.alloc(c->d_rays, sizeof(unsigned) * (size_t)num_streams * levels * max_points);
+    c->mem.alloc(c->d_segs, sizeof(uint4) * (size_t)c->seg_cap * c->opt.nq);
+    c->mem.alloc(c->d_items, sizeof(WorkItem) * (size_t)c->item_cap * c->opt.nq);
+    c->mem.alloc(c->d_wholes, sizeof(WorkItem) * (size_t)num_streams * levels * c->opt.nq);
+    c->mem.alloc(c->d_wq, sizeof(WorkQueue) * c->opt.nq);
     for (int p = 0; p < MAX_PARTS; ++p)
-        for (int i = 0; i < 2; ++i)
-            if ((e = hipMalloc(&c->wl[p][i], sizeof(int) * (4 + (size_t)num_streams))) != hipSuccess) {
-                hs_destroy(c);
-                return fail(HS_ENOMEM, "hipMalloc(update list)", e);
-            }
+        for (int i = 0; i < 2; ++i) c->mem.alloc(c->wl[p][i], sizeof(int) * (4 + (size_t)num_streams));
+    if ((e = c->mem.error) != hipSuccess) {
+        hs_destroy(c);
+        return hs_err.fail(HS_ENOMEM, "hipMalloc", e);
+    }
     {
         WorkQueue q;
         memset(&q, 0, sizeof(q));
@@ -533,7 +461,7 @@ int hs_create(hs_ctx **out, int num_streams, float map_resolution, int map_size_
         for (int p = 0; p < c->opt.nq; ++p) {
             if ((e = hipMemcpy(c->d_wq + p, &q, sizeof(q), hipMemcpyHostToDevice)) != hipSuccess) {
                 hs_destroy(c);
-                return fail(HS_EHIP, "hipMemcpy(work queue)", e);
+                return hs_err.fail(HS_EHIP, "hipMemcpy(work queue)", e);
             }
         }
     }
@@ -550,60 +478,31 @@ int hs_destroy(hs_ctx *c)
 {
     if (!c) return HS_OK;
     hipDeviceSynchronize();  // device work of the context may be on any stream (*_device calls)
-    hipFree(c->d_cells);
-    hipFree(c->d_state);
-    hipFree(c->d_pts1);
-    hipFree(c->d_n1);
-    hipFree(c->d_origo1);
-    hipFree(c->d_hint1);
-    hipFree(c->d_out_pose);
-    hipFree(c->d_out_cov);
-    hipFree(c->d_occ);
-    hipFree(c->d_rays);
-    hipFree(c->d_segs);
-    hipFree(c->d_items);
-    hipFree(c->d_wholes);
-    hipFree(c->d_wq);
-    for (int p = 0; p < MAX_PARTS; ++p)
-        for (int i = 0; i < 2; ++i) hipFree(c->wl[p][i]);
-    hipFree(c->d_cs);
-    hipFree(c->d_ixy);
-    hipFree(c->d_in);
-    hipFree(c->d_iorigo);
-    hipFree(c->d_ranges1);
-    hipFree(c->d_clk);
-    for (auto &p : c->ev_used) {
-        hipEventDestroy(p.a);
-        hipEventDestroy(p.b);
-    }
-    for (auto &p : c->ev_free) {
-        hipEventDestroy(p.a);
-        hipEventDestroy(p.b);
-    }
+    c->mem.free_all();
+    c->timer.destroy();
     for (int p = 0; p < MAX_PARTS; ++p) {
         if (c->pstream[p]) hipStreamDestroy(c->pstream[p]);
         if (c->ev_done[p]) hipEventDestroy(c->ev_done[p]);
         if (c->ev_upd[p]) hipEventDestroy(c->ev_upd[p]);
     }
     if (c->ev_start) hipEventDestroy(c->ev_start);
-    if (c->ev_last) hipEventDestroy(c->ev_last);
-    if (c->stream) hipStreamDestroy(c->stream);
+    c->order.destroy();
     delete c;
     return HS_OK;
 }
 
 int hs_reset(hs_ctx *c)
 {
-    if (!c) return fail(HS_EINVAL, "ctx is NULL");
-    LOCK(c);
-    HCHK(hipDeviceSynchronize());
+    if (!c) return hs_err.fail(HS_EINVAL, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(c->order.mu);
+    S2D_CHK(hs_err, HS_EHIP, hipDeviceSynchronize());
     return reset_all(c, false);
 }
 
 int hs_set_update_factors(hs_ctx *c, float free_factor, float occupied_factor)
 {
-    if (!c) return fail(HS_EINVAL, "ctx is NULL");
-    LOCK(c);
+    if (!c) return hs_err.fail(HS_EINVAL, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(c->order.mu);
     c->geom.lf = prob_to_logodds(free_factor);
     c->geom.lo = prob_to_logodds(occupied_factor);
     return HS_OK;
@@ -611,8 +510,8 @@ int hs_set_update_factors(hs_ctx *c, float free_factor, float occupied_factor)
 
 int hs_set_map_update_thresholds(hs_ctx *c, float min_dist, float min_angle)
 {
-    if (!c) return fail(HS_EINVAL, "ctx is NULL");
-    LOCK(c);
+    if (!c) return hs_err.fail(HS_EINVAL, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(c->order.mu);
     c->geom.min_dist = min_dist;
     c->geom.min_ang = min_angle;
     return HS_OK;
@@ -620,21 +519,21 @@ int hs_set_map_update_thresholds(hs_ctx *c, float min_dist, float min_angle)
 
 int hs_get_scale_to_map(hs_ctx *c, float *scale_out)
 {
-    if (!c || !scale_out) return fail(HS_EINVAL, "NULL argument");
+    if (!c || !scale_out) return hs_err.fail(HS_EINVAL, "NULL argument");
     *scale_out = c->geom.lv[0].scale;
     return HS_OK;
 }
 
 int hs_get_map_levels(hs_ctx *c, int *levels_out)
 {
-    if (!c || !levels_out) return fail(HS_EINVAL, "NULL argument");
+    if (!c || !levels_out) return hs_err.fail(HS_EINVAL, "NULL argument");
     *levels_out = c->levels;
     return HS_OK;
 }
 
 int hs_get_map_info(hs_ctx *c, int level, int *size_x, int *size_y, float *cell_length, float *origin_xy)
 {
-    if (!c || level < 0 || level >= c->levels) return fail(HS_EINVAL, "bad level");
+    if (!c || level < 0 || level >= c->levels) return hs_err.fail(HS_EINVAL, "bad level");
     const LevelGeom &L = c->geom.lv[level];
     if (size_x) *size_x = L.sx;
     if (size_y) *size_y = L.sy;
@@ -650,18 +549,18 @@ int hs_get_map_info(hs_ctx *c, int level, int *size_x, int *size_y, float *cell_
 int hs_update(hs_ctx *c, int stream, const float *xy, int n, float ox, float oy, const float *hint,
               int map_without_matching, float pose_out[3], float cov_out[9], int *did_update_out)
 {
-    if (check_stream(c, stream) != HS_OK) return fail(HS_EINVAL, "bad ctx/stream");
-    LOCK(c);
-    int rc = dev_enter(c, c->stream);
+    if (check_stream(c, stream) != HS_OK) return hs_err.fail(HS_EINVAL, "bad ctx/stream");
+    StreamCall call(c->order, hs_err, nullptr);
+    int rc = call.begin();
     if (rc == HS_OK) rc = stage_scan(c, xy, n, ox, oy, hint);
-    if (rc != HS_OK) return rc;
-    rc = launch_step(c, stream, 1, c->d_pts1, c->max_points, c->d_n1, c->d_origo1, hint ? c->d_hint1 : nullptr,
-                     map_without_matching ? MODE_NO_MATCH_FORCE : MODE_PROCESS, c->d_out_pose, c->d_out_cov, c->stream);
-    if (rc == HS_OK) rc = dev_leave(c, c->stream);
+    if (rc == HS_OK)
+        rc = launch_step(c, stream, 1, c->d_pts1, c->max_points, c->d_n1, c->d_origo1, hint ? c->d_hint1 : nullptr,
+                         map_without_matching ? MODE_NO_MATCH_FORCE : MODE_PROCESS, c->d_out_pose, c->d_out_cov, call.s);
+    if (rc == HS_OK) rc = call.done();
     if (rc != HS_OK) return rc;
     StreamState st;
-    HCHK(hipMemcpyAsync(&st, c->d_state + stream, sizeof(st), hipMemcpyDeviceToHost, c->stream));
-    HCHK(hipStreamSynchronize(c->stream));
+    S2D_CHK(hs_err, HS_EHIP, hipMemcpyAsync(&st, c->d_state + stream, sizeof(st), hipMemcpyDeviceToHost, c->order.stream));
+    S2D_CHK(hs_err, HS_EHIP, hipStreamSynchronize(c->order.stream));
     if (pose_out) memcpy(pose_out, st.pose, sizeof(float) * 3);
     if (cov_out) memcpy(cov_out, st.cov, sizeof(float) * 9);
     if (did_update_out) *did_update_out = st.do_update;
@@ -671,19 +570,19 @@ int hs_update(hs_ctx *c, int stream, const float *xy, int n, float ox, float oy,
 int hs_match(hs_ctx *c, int stream, const float *xy, int n, float ox, float oy, const float hint[3], float pose_out[3],
              float cov_out[9])
 {
-    if (check_stream(c, stream) != HS_OK || !hint) return fail(HS_EINVAL, "bad ctx/stream/hint");
-    LOCK(c);
-    int rc = dev_enter(c, c->stream);
+    if (check_stream(c, stream) != HS_OK || !hint) return hs_err.fail(HS_EINVAL, "bad ctx/stream/hint");
+    StreamCall call(c->order, hs_err, nullptr);
+    int rc = call.begin();
     if (rc == HS_OK) rc = stage_scan(c, xy, n, ox, oy, hint);
-    if (rc != HS_OK) return rc;
-    rc = launch_step(c, stream, 1, c->d_pts1, c->max_points, c->d_n1, c->d_origo1, c->d_hint1, MODE_MATCH_ONLY,
-                     c->d_out_pose, c->d_out_cov, c->stream);
-    if (rc == HS_OK) rc = dev_leave(c, c->stream);
+    if (rc == HS_OK)
+        rc = launch_step(c, stream, 1, c->d_pts1, c->max_points, c->d_n1, c->d_origo1, c->d_hint1, MODE_MATCH_ONLY,
+                         c->d_out_pose, c->d_out_cov, call.s);
+    if (rc == HS_OK) rc = call.done();
     if (rc != HS_OK) return rc;
     float p[3], cv[9];
-    HCHK(hipMemcpyAsync(p, c->d_out_pose, sizeof(p), hipMemcpyDeviceToHost, c->stream));
-    HCHK(hipMemcpyAsync(cv, c->d_out_cov, sizeof(cv), hipMemcpyDeviceToHost, c->stream));
-    HCHK(hipStreamSynchronize(c->stream));
+    S2D_CHK(hs_err, HS_EHIP, hipMemcpyAsync(p, c->d_out_pose, sizeof(p), hipMemcpyDeviceToHost, c->order.stream));
+    S2D_CHK(hs_err, HS_EHIP, hipMemcpyAsync(cv, c->d_out_cov, sizeof(cv), hipMemcpyDeviceToHost, c->order.stream));
+    S2D_CHK(hs_err, HS_EHIP, hipStreamSynchronize(c->order.stream));
     if (pose_out) memcpy(pose_out, p, sizeof(p));
     if (cov_out) memcpy(cov_out, cv, sizeof(cv));
     return HS_OK;
@@ -691,27 +590,27 @@ int hs_match(hs_ctx *c, int stream, const float *xy, int n, float ox, float oy, 
 
 int hs_update_by_scan(hs_ctx *c, int stream, const float *xy, int n, float ox, float oy, const float pose[3])
 {
-    if (check_stream(c, stream) != HS_OK || !pose) return fail(HS_EINVAL, "bad ctx/stream/pose");
-    LOCK(c);
-    int rc = dev_enter(c, c->stream);
+    if (check_stream(c, stream) != HS_OK || !pose) return hs_err.fail(HS_EINVAL, "bad ctx/stream/pose");
+    StreamCall call(c->order, hs_err, nullptr);
+    int rc = call.begin();
     if (rc == HS_OK) rc = stage_scan(c, xy, n, ox, oy, pose);
+    if (rc == HS_OK)
+        rc = launch_step(c, stream, 1, c->d_pts1, c->max_points, c->d_n1, c->d_origo1, c->d_hint1, MODE_UPDATE_ONLY,
+                         nullptr, nullptr, call.s);
+    if (rc == HS_OK) rc = call.done();
     if (rc != HS_OK) return rc;
-    rc = launch_step(c, stream, 1, c->d_pts1, c->max_points, c->d_n1, c->d_origo1, c->d_hint1, MODE_UPDATE_ONLY,
-                     nullptr, nullptr, c->stream);
-    if (rc == HS_OK) rc = dev_leave(c, c->stream);
-    if (rc != HS_OK) return rc;
-    HCHK(hipStreamSynchronize(c->stream));
+    S2D_CHK(hs_err, HS_EHIP, hipStreamSynchronize(c->order.stream));
     return HS_OK;
 }
 
 int hs_get_last_pose(hs_ctx *c, int stream, float pose_out[3], float cov_out[9])
 {
-    if (check_stream(c, stream) != HS_OK) return fail(HS_EINVAL, "bad ctx/stream");
-    LOCK(c);
-    if (dev_enter(c, c->stream) != HS_OK) return HS_EHIP;
+    if (check_stream(c, stream) != HS_OK) return hs_err.fail(HS_EINVAL, "bad ctx/stream");
+    StreamCall call(c->order, hs_err, nullptr);
+    if (call.begin() != HS_OK) return HS_EHIP;
     StreamState st;
-    HCHK(hipMemcpyAsync(&st, c->d_state + stream, sizeof(st), hipMemcpyDeviceToHost, c->stream));
-    HCHK(hipStreamSynchronize(c->stream));
+    S2D_CHK(hs_err, HS_EHIP, hipMemcpyAsync(&st, c->d_state + stream, sizeof(st), hipMemcpyDeviceToHost, c->order.stream));
+    S2D_CHK(hs_err, HS_EHIP, hipStreamSynchronize(c->order.stream));
     if (pose_out) memcpy(pose_out, st.pose, sizeof(float) * 3);
     if (cov_out) memcpy(cov_out, st.cov, sizeof(float) * 9);
     return HS_OK;
@@ -719,12 +618,12 @@ int hs_get_last_pose(hs_ctx *c, int stream, float pose_out[3], float cov_out[9])
 
 int hs_get_clamp_count(hs_ctx *c, int stream, int *out)
 {
-    if (check_stream(c, stream) != HS_OK || !out) return fail(HS_EINVAL, "bad ctx/stream/pointer");
-    LOCK(c);
-    if (dev_enter(c, c->stream) != HS_OK) return HS_EHIP;
+    if (check_stream(c, stream) != HS_OK || !out) return hs_err.fail(HS_EINVAL, "bad ctx/stream/pointer");
+    StreamCall call(c->order, hs_err, nullptr);
+    if (call.begin() != HS_OK) return HS_EHIP;
     StreamState st;
-    HCHK(hipMemcpyAsync(&st, c->d_state + stream, sizeof(st), hipMemcpyDeviceToHost, c->stream));
-    HCHK(hipStreamSynchronize(c->stream));
+    S2D_CHK(hs_err, HS_EHIP, hipMemcpyAsync(&st, c->d_state + stream, sizeof(st), hipMemcpyDeviceToHost, c->order.stream));
+    S2D_CHK(hs_err, HS_EHIP, hipStreamSynchronize(c->order.stream));
     *out = st.clamp_count;
     return HS_OK;
 }
@@ -732,28 +631,28 @@ int hs_get_clamp_count(hs_ctx *c, int stream, int *out)
 int hs_get_map(hs_ctx *c, int stream, int level, int8_t *occ_out, float *logodds_out, int32_t *upd_out,
                int *update_index_out)
 {
-    if (check_stream(c, stream) != HS_OK || level < 0 || level >= c->levels) return fail(HS_EINVAL, "bad stream/level");
-    LOCK(c);
-    if (dev_enter(c, c->stream) != HS_OK) return HS_EHIP;
+    if (check_stream(c, stream) != HS_OK || level < 0 || level >= c->levels) return hs_err.fail(HS_EINVAL, "bad stream/level");
+    StreamCall call(c->order, hs_err, nullptr);
+    if (call.begin() != HS_OK) return HS_EHIP;
     const LevelGeom &L = c->geom.lv[level];
     const size_t ncell = (size_t)L.sx * L.sy;
     const size_t nwords = (size_t)L.tiles_x * L.tiles_y * TILE_BLOCK_WORDS;
     const float *base = c->d_cells + (size_t)stream * c->geom.stream_words + L.word_offset;
     if (occ_out) {
-        hipLaunchKernelGGL(hs_publish_kernel, dim3(1024), dim3(256), 0, c->stream, base, L, c->d_occ);
-        HCHK(hipGetLastError());
-        HCHK(hipMemcpyAsync(occ_out, c->d_occ, ncell, hipMemcpyDeviceToHost, c->stream));
+        hipLaunchKernelGGL(hs_publish_kernel, dim3(1024), dim3(256), 0, c->order.stream, base, L, c->d_occ);
+        S2D_CHK(hs_err, HS_EHIP, hipGetLastError());
+        S2D_CHK(hs_err, HS_EHIP, hipMemcpyAsync(occ_out, c->d_occ, ncell, hipMemcpyDeviceToHost, c->order.stream));
     }
     std::vector<float> tmp;
     if (logodds_out || upd_out) {
         tmp.resize(nwords);
-        HCHK(hipMemcpyAsync(tmp.data(), base, sizeof(float) * nwords, hipMemcpyDeviceToHost, c->stream));
+        S2D_CHK(hs_err, HS_EHIP, hipMemcpyAsync(tmp.data(), base, sizeof(float) * nwords, hipMemcpyDeviceToHost, c->order.stream));
     }
     StreamState st;
-    HCHK(hipMemcpyAsync(&st, c->d_state + stream, sizeof(st), hipMemcpyDeviceToHost, c->stream));
-    HCHK(hipStreamSynchronize(c->stream));
+    S2D_CHK(hs_err, HS_EHIP, hipMemcpyAsync(&st, c->d_state + stream, sizeof(st), hipMemcpyDeviceToHost, c->order.stream));
+    S2D_CHK(hs_err, HS_EHIP, hipStreamSynchronize(c->order.stream));
     if (upd_out && st.ord_overflow)
-        return fail(HS_ESTATE, "stream's update ordinals overflowed 16 bits: more than 32000 map updates without the "
+        return hs_err.fail(HS_ESTATE, "stream's update ordinals overflowed 16 bits: more than 32000 map updates without the "
                                "library's ordinal sweep (replayed graph captures of *_device calls?); call "
                                "hs_flush_ordinals at least every 32000 steps; hs_reset clears the state");
     if (!tmp.empty()) {
@@ -779,15 +678,15 @@ int hs_get_map(hs_ctx *c, int stream, int level, int8_t *occ_out, float *logodds
 int hs_set_map(hs_ctx *c, int stream, int level, const float *logodds, const int32_t *upd)
 {
     if (check_stream(c, stream) != HS_OK || level < 0 || level >= c->levels || !logodds || !upd)
-        return fail(HS_EINVAL, "bad arguments");
-    LOCK(c);
-    if (dev_enter(c, c->stream) != HS_OK) return HS_EHIP;
+        return hs_err.fail(HS_EINVAL, "bad arguments");
+    StreamCall call(c->order, hs_err, nullptr);
+    if (call.begin() != HS_OK) return HS_EHIP;
     const LevelGeom &L = c->geom.lv[level];
     const size_t nwords = (size_t)L.tiles_x * L.tiles_y * TILE_BLOCK_WORDS;
     float *base = c->d_cells + (size_t)stream * c->geom.stream_words + L.word_offset;
     std::vector<float> tmp(nwords);
-    HCHK(hipMemcpyAsync(tmp.data(), base, sizeof(float) * nwords, hipMemcpyDeviceToHost, c->stream));
-    HCHK(hipStreamSynchronize(c->stream));
+    S2D_CHK(hs_err, HS_EHIP, hipMemcpyAsync(tmp.data(), base, sizeof(float) * nwords, hipMemcpyDeviceToHost, c->order.stream));
+    S2D_CHK(hs_err, HS_EHIP, hipStreamSynchronize(c->order.stream));
     for (int y = 0; y < L.sy; ++y)
         for (int x = 0; x < L.sx; ++x) {
             const size_t w = cell_word(L, x, y), o = (size_t)y * L.sx + x;
@@ -797,8 +696,8 @@ int hs_set_map(hs_ctx *c, int stream, int level, const float *logodds, const int
             const uint16_t zero = 0;
             memcpy(reinterpret_cast<char *>(&tmp[tb + ORD_OFF]) + 2 * ci, &zero, sizeof(zero));  // ... in effect
         }
-    HCHK(hipMemcpyAsync(base, tmp.data(), sizeof(float) * nwords, hipMemcpyHostToDevice, c->stream));
-    HCHK(hipStreamSynchronize(c->stream));
+    S2D_CHK(hs_err, HS_EHIP, hipMemcpyAsync(base, tmp.data(), sizeof(float) * nwords, hipMemcpyHostToDevice, c->order.stream));
+    S2D_CHK(hs_err, HS_EHIP, hipStreamSynchronize(c->order.stream));
     return HS_OK;
 }
 
@@ -807,33 +706,32 @@ int hs_step_batch_device(hs_ctx *c, int stream_begin, int count, const float *d_
 {
     if (!c || stream_begin < 0 || count < 0 || stream_begin + count > c->B || !d_xy || !d_n ||
         xy_stride < c->max_points)
-        return fail(HS_EINVAL, "bad batch arguments (xy_stride must be >= max_points)");
-    LOCK(c);
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    int rc = dev_enter(c, s);
+        return hs_err.fail(HS_EINVAL, "bad batch arguments (xy_stride must be >= max_points)");
+    StreamCall call(c->order, hs_err, hip_stream);
+    int rc = call.begin();
     if (rc == HS_OK)
         rc = launch_step(c, stream_begin, count, (const float2 *)d_xy, xy_stride, d_n, (const float2 *)d_origo, d_hints,
-                         MODE_PROCESS, nullptr, nullptr, s);
-    return rc == HS_OK ? dev_leave(c, s) : rc;
+                         MODE_PROCESS, nullptr, nullptr, call.s);
+    return rc == HS_OK ? call.done() : rc;
 }
 
 int hs_run_ranges_device(hs_ctx *c, int steps, const float *d_ranges, int range_stride, size_t step_stride,
                          void *hip_stream)
 {
-    if (!c || steps < 0 || (steps > 0 && !d_ranges)) return fail(HS_EINVAL, "bad run arguments");
-    LOCK(c);
-    if (!c->has_laser) return fail(HS_EINVAL, "hs_set_laser not called");
+    if (!c || steps < 0 || (steps > 0 && !d_ranges)) return hs_err.fail(HS_EINVAL, "bad run arguments");
+    StreamCall call(c->order, hs_err, hip_stream);
+    if (!c->has_laser) return hs_err.fail(HS_EINVAL, "hs_set_laser not called");
     if (range_stride < c->ingest.n || step_stride < (size_t)range_stride * c->B)
-        return fail(HS_EINVAL, "range_stride < n_beams or step_stride < num_streams * range_stride");
+        return hs_err.fail(HS_EINVAL, "range_stride < n_beams or step_stride < num_streams * range_stride");
     if (steps == 0) return HS_OK;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    int rc = dev_enter(c, s);
+    const hipStream_t s = call.s;
+    int rc = call.begin();
     if (rc != HS_OK) return rc;
     if (!plan_pipeline(c->opt, shape(c))) {  // default: the steps in order on s
         for (int k = 0; k < steps && rc == HS_OK; ++k)
             rc = launch_ranges_step(c, 0, c->B, d_ranges + (size_t)k * step_stride, range_stride, c->d_ixy, c->max_points,
                                     c->d_in, c->d_iorigo, nullptr, nullptr, nullptr, s);
-        return rc == HS_OK ? dev_leave(c, s) : rc;
+        return rc == HS_OK ? call.done() : rc;
     }
     // Two halves of the fleet on part streams 0 / 1.  Per step and half: ingest, match, then the grid
     // update once the OTHER half's previous update has finished, so that the updates alternate and each
@@ -841,19 +739,19 @@ int hs_run_ranges_device(hs_ctx *c, int steps, const float *d_ranges, int range_
     // independent, so the results equal the in-order steps bit for bit.
     const int h0 = (c->B + 1) / 2;
     const int beg[2] = {0, h0}, cnt[2] = {h0, c->B - h0};
-    HCHK(hipEventRecord(c->ev_start, s));
-    for (int h = 0; h < 2; ++h) HCHK(hipStreamWaitEvent(c->pstream[h], c->ev_start, 0));
+    S2D_CHK(hs_err, HS_EHIP, hipEventRecord(c->ev_start, s));
+    for (int h = 0; h < 2; ++h) S2D_CHK(hs_err, HS_EHIP, hipStreamWaitEvent(c->pstream[h], c->ev_start, 0));
     for (int k = 0; k < steps && rc == HS_OK; ++k) {
         const float *rk = d_ranges + (size_t)k * step_stride;
         if (c->ord_steps + 1 > c->opt.ord_interval) {
             // an ordinal sweep is due: after both halves' previous updates, before either half's next step
             for (int h = 0; h < 2; ++h) {
-                HCHK(hipEventRecord(c->ev_done[h], c->pstream[h]));
-                HCHK(hipStreamWaitEvent(s, c->ev_done[h], 0));
+                S2D_CHK(hs_err, HS_EHIP, hipEventRecord(c->ev_done[h], c->pstream[h]));
+                S2D_CHK(hs_err, HS_EHIP, hipStreamWaitEvent(s, c->ev_done[h], 0));
             }
             if ((rc = ord_sweep_if_due(c, s)) != HS_OK) break;
-            HCHK(hipEventRecord(c->ev_start, s));
-            for (int h = 0; h < 2; ++h) HCHK(hipStreamWaitEvent(c->pstream[h], c->ev_start, 0));
+            S2D_CHK(hs_err, HS_EHIP, hipEventRecord(c->ev_start, s));
+            for (int h = 0; h < 2; ++h) S2D_CHK(hs_err, HS_EHIP, hipStreamWaitEvent(c->pstream[h], c->ev_start, 0));
         } else {
             ++c->ord_steps;
         }
@@ -866,14 +764,14 @@ int hs_run_ranges_device(hs_ctx *c, int steps, const float *d_ranges, int range_
             hipEvent_t wait = (h == 1 || k > 0) ? c->ev_upd[h ^ 1] : nullptr;
             rc = launch_part(c, h, beg[h], cnt[h], xy, c->max_points, c->d_in + beg[h], c->d_iorigo + beg[h], nullptr,
                              MODE_PROCESS, nullptr, nullptr, ps, wait);
-            if (rc == HS_OK && hipEventRecord(c->ev_upd[h], ps) != hipSuccess) rc = fail(HS_EHIP, "hipEventRecord");
+            if (rc == HS_OK && hipEventRecord(c->ev_upd[h], ps) != hipSuccess) rc = hs_err.fail(HS_EHIP, "hipEventRecord");
         }
     }
     for (int h = 0; h < 2; ++h) {
-        HCHK(hipEventRecord(c->ev_done[h], c->pstream[h]));
-        HCHK(hipStreamWaitEvent(s, c->ev_done[h], 0));
+        S2D_CHK(hs_err, HS_EHIP, hipEventRecord(c->ev_done[h], c->pstream[h]));
+        S2D_CHK(hs_err, HS_EHIP, hipStreamWaitEvent(s, c->ev_done[h], 0));
     }
-    return rc == HS_OK ? dev_leave(c, s) : rc;
+    return rc == HS_OK ? call.done() : rc;
 }
 
 void hs_default_laser(hs_laser *L, int n_beams, float angle_min, float angle_increment)
@@ -895,9 +793,23 @@ void hs_default_laser(hs_laser *L, int n_beams, float angle_min, float angle_inc
 
 int hs_set_laser(hs_ctx *c, const hs_laser *L, const double *unit_vectors)
 {
-    if (!c || !L) return fail(HS_EINVAL, "NULL argument");
-    LOCK(c);
-    if (L->n_beams < 0 || L->n_beams > c->max_points) return fail(HS_EINVAL, "n_beams must be in [0, max_points]");
+    if (!c || !L) return hs_err.fail(HS_EINVAL, "NULL argument");
+    StreamCall call(c->order, hs_err, nullptr);
+    if (L->n_beams < 0 || L->n_beams > c->max_points) return hs_err.fail(HS_EINVAL, "n_beams must be in [0, max_points]");
+    if (!c->d_cs) {  // the first call's ingest buffers, all four or none: a failed call leaves the context as it was
+        c->mem.alloc(c->d_cs, sizeof(double2) * (size_t)c->max_points);
+        c->mem.alloc(c->d_in, sizeof(int) * (size_t)c->B);
+        c->mem.alloc(c->d_iorigo, sizeof(float2) * (size_t)c->B);
+        c->mem.alloc(c->d_ranges1, sizeof(float) * (size_t)c->max_points);
+        const hipError_t e = c->mem.take_error();
+        if (e != hipSuccess) {
+            c->mem.free(c->d_cs);
+            c->mem.free(c->d_in);
+            c->mem.free(c->d_iorigo);
+            c->mem.free(c->d_ranges1);
+            return hs_err.fail(HS_ENOMEM, "hipMalloc(ingest)", e);
+        }
+    }
     IngestGeom &g = c->ingest;
     g.n = L->n_beams;
     g.cutoff = L->range_cutoff;
@@ -922,18 +834,10 @@ int hs_set_laser(hs_ctx *c, const hs_laser *L, const double *unit_vectors)
             cs[2 * i + 1] = sin(a);
         }
     }
-    hipError_t e;
-    if (!c->d_cs) {
-        if ((e = hipMalloc(&c->d_cs, sizeof(double2) * (size_t)c->max_points)) != hipSuccess ||
-            (e = hipMalloc(&c->d_in, sizeof(int) * (size_t)c->B)) != hipSuccess ||
-            (e = hipMalloc(&c->d_iorigo, sizeof(float2) * (size_t)c->B)) != hipSuccess ||
-            (e = hipMalloc(&c->d_ranges1, sizeof(float) * (size_t)c->max_points)) != hipSuccess)
-            return fail(HS_ENOMEM, "hipMalloc(ingest)", e);
-    }
-    if (dev_enter(c, c->stream) != HS_OK) return HS_EHIP;
+    if (call.begin() != HS_OK) return HS_EHIP;
     if (L->n_beams > 0)
-        HCHK(hipMemcpyAsync(c->d_cs, cs.data(), sizeof(double2) * L->n_beams, hipMemcpyHostToDevice, c->stream));
-    HCHK(hipStreamSynchronize(c->stream));
+        S2D_CHK(hs_err, HS_EHIP, hipMemcpyAsync(c->d_cs, cs.data(), sizeof(double2) * L->n_beams, hipMemcpyHostToDevice, call.s));
+    S2D_CHK(hs_err, HS_EHIP, hipStreamSynchronize(call.s));
     c->has_laser = true;
     return HS_OK;
 }
@@ -941,52 +845,51 @@ int hs_set_laser(hs_ctx *c, const hs_laser *L, const double *unit_vectors)
 int hs_ingest_batch_device(hs_ctx *c, int count, const float *d_ranges, int range_stride, float *d_xy, int xy_stride,
                            int *d_n, float *d_origo, void *hip_stream)
 {
-    if (!c || count < 0 || (count > 0 && (!d_ranges || !d_xy || !d_n))) return fail(HS_EINVAL, "bad ingest arguments");
-    LOCK(c);
-    if (!c->has_laser) return fail(HS_EINVAL, "hs_set_laser not called");
-    if (range_stride < c->ingest.n || xy_stride < c->ingest.n) return fail(HS_EINVAL, "stride < n_beams");
+    if (!c || count < 0 || (count > 0 && (!d_ranges || !d_xy || !d_n))) return hs_err.fail(HS_EINVAL, "bad ingest arguments");
+    StreamCall call(c->order, hs_err, hip_stream);
+    if (!c->has_laser) return hs_err.fail(HS_EINVAL, "hs_set_laser not called");
+    if (range_stride < c->ingest.n || xy_stride < c->ingest.n) return hs_err.fail(HS_EINVAL, "stride < n_beams");
     if (count == 0) return HS_OK;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    int rc = dev_enter(c, s);
-    if (rc == HS_OK) rc = launch_ingest(c, count, d_ranges, range_stride, (float2 *)d_xy, xy_stride, d_n, (float2 *)d_origo, s);
-    return rc == HS_OK ? dev_leave(c, s) : rc;
+    int rc = call.begin();
+    if (rc == HS_OK)
+        rc = launch_ingest(c, count, d_ranges, range_stride, (float2 *)d_xy, xy_stride, d_n, (float2 *)d_origo, call.s);
+    return rc == HS_OK ? call.done() : rc;
 }
 
 int hs_step_ranges_batch_device(hs_ctx *c, int stream_begin, int count, const float *d_ranges, int range_stride,
                                 const float *d_hints, void *hip_stream)
 {
-    if (!c || stream_begin < 0 || count < 0 || stream_begin + count > c->B) return fail(HS_EINVAL, "bad batch arguments");
-    LOCK(c);
-    if (!c->has_laser) return fail(HS_EINVAL, "hs_set_laser not called");
-    if (count > 0 && !d_ranges) return fail(HS_EINVAL, "d_ranges is NULL");
-    if (range_stride < c->ingest.n) return fail(HS_EINVAL, "range_stride < n_beams");
+    if (!c || stream_begin < 0 || count < 0 || stream_begin + count > c->B) return hs_err.fail(HS_EINVAL, "bad batch arguments");
+    StreamCall call(c->order, hs_err, hip_stream);
+    if (!c->has_laser) return hs_err.fail(HS_EINVAL, "hs_set_laser not called");
+    if (count > 0 && !d_ranges) return hs_err.fail(HS_EINVAL, "d_ranges is NULL");
+    if (range_stride < c->ingest.n) return hs_err.fail(HS_EINVAL, "range_stride < n_beams");
     if (count == 0) return HS_OK;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    int rc = dev_enter(c, s);
+    int rc = call.begin();
     if (rc == HS_OK)
         rc = launch_ranges_step(c, stream_begin, count, d_ranges, range_stride,
                                 c->d_ixy + (size_t)stream_begin * c->max_points, c->max_points, c->d_in, c->d_iorigo,
-                                d_hints, nullptr, nullptr, s);
-    return rc == HS_OK ? dev_leave(c, s) : rc;
+                                d_hints, nullptr, nullptr, call.s);
+    return rc == HS_OK ? call.done() : rc;
 }
 
 int hs_update_ranges(hs_ctx *c, int stream, const float *ranges, float pose_out[3], float cov_out[9], int *did_update_out)
 {
-    if (check_stream(c, stream) != HS_OK) return fail(HS_EINVAL, "bad ctx/stream");
-    LOCK(c);
-    if (!c->has_laser) return fail(HS_EINVAL, "hs_set_laser not called");
-    if (c->ingest.n > 0 && !ranges) return fail(HS_EINVAL, "ranges is NULL");
-    if (dev_enter(c, c->stream) != HS_OK) return HS_EHIP;
+    if (check_stream(c, stream) != HS_OK) return hs_err.fail(HS_EINVAL, "bad ctx/stream");
+    StreamCall call(c->order, hs_err, nullptr);
+    if (!c->has_laser) return hs_err.fail(HS_EINVAL, "hs_set_laser not called");
+    if (c->ingest.n > 0 && !ranges) return hs_err.fail(HS_EINVAL, "ranges is NULL");
+    if (call.begin() != HS_OK) return HS_EHIP;
     if (c->ingest.n > 0)
-        HCHK(hipMemcpyAsync(c->d_ranges1, ranges, sizeof(float) * c->ingest.n, hipMemcpyHostToDevice, c->stream));
+        S2D_CHK(hs_err, HS_EHIP, hipMemcpyAsync(c->d_ranges1, ranges, sizeof(float) * c->ingest.n, hipMemcpyHostToDevice, c->order.stream));
     // scanCallback: startEstimate = getLastScanMatchPose() (hector_slam.cc:201), i.e. no explicit hint
     int rc = launch_ranges_step(c, stream, 1, c->d_ranges1, c->max_points, c->d_ixy + (size_t)stream * c->max_points,
-                                c->max_points, c->d_n1, c->d_origo1, nullptr, c->d_out_pose, c->d_out_cov, c->stream);
-    if (rc == HS_OK) rc = dev_leave(c, c->stream);
+                                c->max_points, c->d_n1, c->d_origo1, nullptr, c->d_out_pose, c->d_out_cov, c->order.stream);
+    if (rc == HS_OK) rc = call.done();
     if (rc != HS_OK) return rc;
     StreamState st;
-    HCHK(hipMemcpyAsync(&st, c->d_state + stream, sizeof(st), hipMemcpyDeviceToHost, c->stream));
-    HCHK(hipStreamSynchronize(c->stream));
+    S2D_CHK(hs_err, HS_EHIP, hipMemcpyAsync(&st, c->d_state + stream, sizeof(st), hipMemcpyDeviceToHost, c->order.stream));
+    S2D_CHK(hs_err, HS_EHIP, hipStreamSynchronize(c->order.stream));
     if (pose_out) memcpy(pose_out, st.pose, sizeof(float) * 3);
     if (cov_out) memcpy(cov_out, st.cov, sizeof(float) * 9);
     if (did_update_out) *did_update_out = st.do_update;
@@ -995,11 +898,11 @@ int hs_update_ranges(hs_ctx *c, int stream, const float *ranges, float pose_out[
 
 int hs_get_poses(hs_ctx *c, float *poses_out, float *covs_out, int *did_update_out, int64_t *cells_out)
 {
-    if (!c) return fail(HS_EINVAL, "ctx is NULL");
-    LOCK(c);
+    if (!c) return hs_err.fail(HS_EINVAL, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(c->order.mu);
     std::vector<StreamState> h(c->B);
-    HCHK(hipDeviceSynchronize());
-    HCHK(hipMemcpy(h.data(), c->d_state, sizeof(StreamState) * c->B, hipMemcpyDeviceToHost));
+    S2D_CHK(hs_err, HS_EHIP, hipDeviceSynchronize());
+    S2D_CHK(hs_err, HS_EHIP, hipMemcpy(h.data(), c->d_state, sizeof(StreamState) * c->B, hipMemcpyDeviceToHost));
     for (int s = 0; s < c->B; ++s) {
         if (poses_out) memcpy(poses_out + 3 * s, h[s].pose, sizeof(float) * 3);
         if (covs_out) memcpy(covs_out + 9 * s, h[s].cov, sizeof(float) * 9);
@@ -1011,12 +914,12 @@ int hs_get_poses(hs_ctx *c, float *poses_out, float *covs_out, int *did_update_o
 
 int hs_get_counters(hs_ctx *c, int64_t out[6], int reset)
 {
-    if (!c || !out) return fail(HS_EINVAL, "NULL argument");
-    LOCK(c);
+    if (!c || !out) return hs_err.fail(HS_EINVAL, "NULL argument");
+    std::lock_guard<std::mutex> lock(c->order.mu);
     std::vector<StreamState> h(c->B);
-    HCHK(hipStreamSynchronize(c->stream));
-    HCHK(hipDeviceSynchronize());
-    HCHK(hipMemcpy(h.data(), c->d_state, sizeof(StreamState) * c->B, hipMemcpyDeviceToHost));
+    S2D_CHK(hs_err, HS_EHIP, hipStreamSynchronize(c->order.stream));
+    S2D_CHK(hs_err, HS_EHIP, hipDeviceSynchronize());
+    S2D_CHK(hs_err, HS_EHIP, hipMemcpy(h.data(), c->d_state, sizeof(StreamState) * c->B, hipMemcpyDeviceToHost));
     for (int k = 0; k < 6; ++k) out[k] = 0;
     for (int s = 0; s < c->B; ++s) {
         out[0] += (int64_t)h[s].tot_cells;
@@ -1030,19 +933,19 @@ int hs_get_counters(hs_ctx *c, int64_t out[6], int reset)
             h[s].tot_touched = 0;
         }
     }
-    if (reset) HCHK(hipMemcpy(c->d_state, h.data(), sizeof(StreamState) * c->B, hipMemcpyHostToDevice));
+    if (reset) S2D_CHK(hs_err, HS_EHIP, hipMemcpy(c->d_state, h.data(), sizeof(StreamState) * c->B, hipMemcpyHostToDevice));
     return HS_OK;
 }
 
 int hs_get_queue_stats(hs_ctx *c, int64_t out[8], int reset_stamps)
 {
-    if (!c || !out) return fail(HS_EINVAL, "NULL argument");
-    LOCK(c);
+    if (!c || !out) return hs_err.fail(HS_EINVAL, "NULL argument");
+    std::lock_guard<std::mutex> lock(c->order.mu);
     WorkQueue q[MAX_PARTS];
     unsigned long long st[8];
-    HCHK(hipDeviceSynchronize());
-    HCHK(hipMemcpy(q, c->d_wq, sizeof(WorkQueue) * c->opt.nq, hipMemcpyDeviceToHost));
-    HCHK(hipMemcpyFromSymbol(st, HIP_SYMBOL(g_stamps), sizeof(st)));
+    S2D_CHK(hs_err, HS_EHIP, hipDeviceSynchronize());
+    S2D_CHK(hs_err, HS_EHIP, hipMemcpy(q, c->d_wq, sizeof(WorkQueue) * c->opt.nq, hipMemcpyDeviceToHost));
+    S2D_CHK(hs_err, HS_EHIP, hipMemcpyFromSymbol(st, HIP_SYMBOL(g_stamps), sizeof(st)));
     for (int k = 0; k < 4; ++k) out[k] = 0;
     for (int p = 0; p < c->opt.nq; ++p) {
         out[0] += q[p].item_used;
@@ -1053,42 +956,41 @@ int hs_get_queue_stats(hs_ctx *c, int64_t out[8], int reset_stamps)
     for (int k = 0; k < 4; ++k) out[4 + k] = (int64_t)st[k];
     if (reset_stamps) {
         memset(st, 0, sizeof(st));
-        HCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), st, sizeof(st)));
+        S2D_CHK(hs_err, HS_EHIP, hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), st, sizeof(st)));
     }
     return HS_OK;
 }
 
 int hs_get_diag_stamps(hs_ctx *c, int64_t out[8], int reset)
 {
-    if (!c || !out) return fail(HS_EINVAL, "bad arguments");
-    LOCK(c);
+    if (!c || !out) return hs_err.fail(HS_EINVAL, "bad arguments");
+    std::lock_guard<std::mutex> lock(c->order.mu);
     unsigned long long st[8];
-    HCHK(hipDeviceSynchronize());
-    HCHK(hipMemcpyFromSymbol(st, HIP_SYMBOL(g_stamps), sizeof(st)));
+    S2D_CHK(hs_err, HS_EHIP, hipDeviceSynchronize());
+    S2D_CHK(hs_err, HS_EHIP, hipMemcpyFromSymbol(st, HIP_SYMBOL(g_stamps), sizeof(st)));
     for (int k = 0; k < 8; ++k) out[k] = (int64_t)st[k];
     if (reset) {
         memset(st, 0, sizeof(st));
-        HCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), st, sizeof(st)));
+        S2D_CHK(hs_err, HS_EHIP, hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), st, sizeof(st)));
     }
     return HS_OK;
 }
 
 int hs_flush_ordinals(hs_ctx *c, void *hip_stream)
 {
-    if (!c) return fail(HS_EINVAL, "ctx is NULL");
-    LOCK(c);
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    if (dev_enter(c, s) != HS_OK) return HS_EHIP;
+    if (!c) return hs_err.fail(HS_EINVAL, "ctx is NULL");
+    StreamCall call(c->order, hs_err, hip_stream);
+    if (call.begin() != HS_OK) return HS_EHIP;
     c->ord_steps = c->opt.ord_interval;  // due now
-    const int rc = ord_sweep_if_due(c, s);
+    const int rc = ord_sweep_if_due(c, call.s);
     if (rc != HS_OK) return rc;
     c->ord_steps = 0;  // no step of the new epoch has run yet
-    return dev_leave(c, s);
+    return call.done();
 }
 
 int hs_get_device_buffers(hs_ctx *c, void **cells, size_t *cells_bytes, size_t *stream_words)
 {
-    if (!c) return fail(HS_EINVAL, "ctx is NULL");
+    if (!c) return hs_err.fail(HS_EINVAL, "ctx is NULL");
     if (cells) *cells = c->d_cells;
     if (cells_bytes) *cells_bytes = c->cells_bytes;
     if (stream_words) *stream_words = c->geom.stream_words;
@@ -1097,8 +999,8 @@ int hs_get_device_buffers(hs_ctx *c, void **cells, size_t *cells_bytes, size_t *
 
 int hs_set_pose_log(hs_ctx *c, float *d_buf, int streams, int capacity)
 {
-    if (!c || streams < 0 || capacity < 0 || (d_buf && streams > c->B)) return fail(HS_EINVAL, "bad pose log");
-    LOCK(c);
+    if (!c || streams < 0 || capacity < 0 || (d_buf && streams > c->B)) return hs_err.fail(HS_EINVAL, "bad pose log");
+    std::lock_guard<std::mutex> lock(c->order.mu);
     c->plog.buf = d_buf;
     c->plog.streams = d_buf ? streams : 0;
     c->plog.capacity = d_buf ? capacity : 0;
@@ -1108,8 +1010,8 @@ int hs_set_pose_log(hs_ctx *c, float *d_buf, int streams, int capacity)
 
 int hs_set_pose_log_slots(hs_ctx *c, float *d_buf, const int *d_slot_of_stream, int slots, int capacity)
 {
-    if (!c || slots < 0 || capacity < 0 || (d_buf && !d_slot_of_stream)) return fail(HS_EINVAL, "bad pose log");
-    LOCK(c);
+    if (!c || slots < 0 || capacity < 0 || (d_buf && !d_slot_of_stream)) return hs_err.fail(HS_EINVAL, "bad pose log");
+    std::lock_guard<std::mutex> lock(c->order.mu);
     c->plog.buf = d_buf;
     c->plog.streams = d_buf ? slots : 0;
     c->plog.capacity = d_buf ? capacity : 0;
@@ -1117,63 +1019,47 @@ int hs_set_pose_log_slots(hs_ctx *c, float *d_buf, const int *d_slot_of_stream, 
     return HS_OK;
 }
 
-void *hs_get_stream(hs_ctx *c) { return c ? (void *)c->stream : nullptr; }
+void *hs_get_stream(hs_ctx *c) { return c ? (void *)c->order.stream : nullptr; }
 
 int hs_set_reduction_order(hs_ctx *c, int order)
 {
-    if (!c || (order != HS_ORDER_REFERENCE && order != HS_ORDER_TREE256)) return fail(HS_EINVAL, "bad reduction order");
-    LOCK(c);
+    if (!c || (order != HS_ORDER_REFERENCE && order != HS_ORDER_TREE256)) return hs_err.fail(HS_EINVAL, "bad reduction order");
+    std::lock_guard<std::mutex> lock(c->order.mu);
     c->reduce_order = order;
     return HS_OK;
 }
 
 int hs_get_reduction_order(hs_ctx *c, int *order_out)
 {
-    if (!c || !order_out) return fail(HS_EINVAL, "NULL argument");
+    if (!c || !order_out) return hs_err.fail(HS_EINVAL, "NULL argument");
     *order_out = c->reduce_order;
     return HS_OK;
 }
 
 int hs_set_timing(hs_ctx *c, int enable)
 {
-    if (!c) return fail(HS_EINVAL, "ctx is NULL");
-    LOCK(c);
-    c->timing = enable != 0;
-    return HS_OK;
+    if (!c) return hs_err.fail(HS_EINVAL, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(c->order.mu);
+    return set_timing(c->timer, enable);
 }
 
 int hs_get_kernel_times(hs_ctx *c, double ms_out[3], int64_t launches_out[3], int reset)
 {
-    if (!c) return fail(HS_EINVAL, "ctx is NULL");
-    LOCK(c);
-    for (auto &p : c->ev_used) {
-        HCHK(hipEventSynchronize(p.b));
-        float ms = 0.0f;
-        HCHK(hipEventElapsedTime(&ms, p.a, p.b));
-        c->acc_ms[p.kernel] += ms;
-        c->acc_n[p.kernel] += 1;
-        c->ev_free.push_back(p);
-    }
-    c->ev_used.clear();
-    for (int k = 0; k < NKERN; ++k) {
-        if (ms_out) ms_out[k] = c->acc_ms[k];
-        if (launches_out) launches_out[k] = c->acc_n[k];
-        if (reset) {
-            c->acc_ms[k] = 0.0;
-            c->acc_n[k] = 0;
-        }
-    }
-    return HS_OK;
+    if (!c) return hs_err.fail(HS_EINVAL, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(c->order.mu);
+    return get_kernel_times(c->timer, hs_err, ms_out, launches_out, reset, K_NUM);
 }
 
 int hs_set_clock_probe(hs_ctx *c, int enable)
 {
-    if (!c) return fail(HS_EINVAL, "ctx is NULL");
-    LOCK(c);
+    if (!c) return hs_err.fail(HS_EINVAL, "ctx is NULL");
+    std::lock_guard<std::mutex> lock(c->order.mu);
     if (enable && !c->d_clk) {
-        HCHK(hipMalloc(&c->d_clk, 8 * sizeof(unsigned long long)));
-        HCHK(hipMemsetAsync(c->d_clk, 0, 8 * sizeof(unsigned long long), c->stream));
-        HCHK(hipStreamSynchronize(c->stream));
+        c->mem.alloc(c->d_clk, 8 * sizeof(unsigned long long));
+        const hipError_t e = c->mem.take_error();
+        if (e != hipSuccess) return hs_err.fail(HS_EHIP, "hipMalloc(clock probe)", e);
+        S2D_CHK(hs_err, HS_EHIP, hipMemsetAsync(c->d_clk, 0, 8 * sizeof(unsigned long long), c->order.stream));
+        S2D_CHK(hs_err, HS_EHIP, hipStreamSynchronize(c->order.stream));
     }
     c->geom.clk = enable ? c->d_clk : nullptr;
     return HS_OK;
@@ -1181,19 +1067,19 @@ int hs_set_clock_probe(hs_ctx *c, int enable)
 
 int hs_get_clock_probe(hs_ctx *c, double out[6], int reset)
 {
-    if (!c || !out) return fail(HS_EINVAL, "NULL argument");
-    LOCK(c);
+    if (!c || !out) return hs_err.fail(HS_EINVAL, "NULL argument");
+    std::lock_guard<std::mutex> lock(c->order.mu);
     for (int k = 0; k < 6; ++k) out[k] = 0.0;
     if (!c->d_clk) return HS_OK;
-    HCHK(hipDeviceSynchronize());  // the probed kernels may have run on any stream (*_device calls)
+    S2D_CHK(hs_err, HS_EHIP, hipDeviceSynchronize());  // the probed kernels may have run on any stream (*_device calls)
     unsigned long long h[8];
-    HCHK(hipMemcpy(h, c->d_clk, sizeof(h), hipMemcpyDeviceToHost));
+    S2D_CHK(hs_err, HS_EHIP, hipMemcpy(h, c->d_clk, sizeof(h), hipMemcpyDeviceToHost));
     for (int k = 0; k < 2; ++k) {
         out[3 * k] = (double)h[4 * k];
         out[3 * k + 1] = (double)h[4 * k + 1];
         out[3 * k + 2] = (double)h[4 * k + 2];
     }
-    if (reset) HCHK(hipMemset(c->d_clk, 0, sizeof(h)));
+    if (reset) S2D_CHK(hs_err, HS_EHIP, hipMemset(c->d_clk, 0, sizeof(h)));
     return HS_OK;
 }
 

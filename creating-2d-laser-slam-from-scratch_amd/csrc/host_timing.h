@@ -1,6 +1,6 @@
 // host_timing.h -- per-kernel device timing of a context's launches (host only): a pool of hipEvent pairs around each
-// launch and the accumulated milliseconds / launch counts per kernel.  Used by the six Karto contexts that time their
-// kernels (kt_, kg_, kl_, ke_, kp_, kd_) through stage_runtime.h, which holds the *_set_timing / *_get_kernel_times
+// launch and the accumulated milliseconds / launch counts per kernel.  Used by every context that times its kernels
+// (hs_, gm_, pl_ and the Karto stages) through stage_runtime.h, which holds the *_set_timing / *_get_kernel_times
 // entry points' common part.
 #pragma once
 #include <hip/hip_runtime.h>

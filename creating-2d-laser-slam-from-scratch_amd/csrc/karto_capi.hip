@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "stage_runtime.h"
+#include "karto_graph_mirror.h"  // DeviceEditEpoch
 #include "karto_kernels.hip"
 
 using namespace s2d;

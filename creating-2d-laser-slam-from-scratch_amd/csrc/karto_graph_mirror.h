@@ -2,9 +2,9 @@
 // spa_graph.h): the epoch that tells which of them device-side edits have left behind (EditEpoch), and a mirror
 // rebuilt from a graph's device arrays after such edits: the header's counts and the edge / constraint arrays in
 // insertion order are all a mirror needs, since every other list is compile()'s function of them.  Plain C++, no
-// HIP: karto_loop_capi.hip and spa_capi.hip include it, and so do the stand-alone checks
-// tests/cpp/karto_graph_mirror_check.cpp and tests/cpp/stage_runtime_check.cpp (built with
-// -fsanitize=address,undefined).
+// HIP above the __HIPCC__ line: karto_capi.hip, karto_loop_capi.hip and spa_capi.hip include it, and so do the
+// stand-alone checks tests/cpp/karto_graph_mirror_check.cpp and tests/cpp/stage_runtime_check.cpp (built with
+// -fsanitize=address,undefined).  Below that line: the epoch's device words (DeviceEditEpoch), for those three.
 #pragma once
 #include <cstddef>
 #include <vector>
@@ -63,3 +63,39 @@ inline bool spa_mirror_rebuild(SpaGraph &gr, int n_nodes, const int *ids, const 
 }
 
 }  // namespace s2d
+
+#if defined(__HIPCC__)
+#include "stage_runtime.h"
+
+namespace s2d __attribute__((visibility("hidden"))) {
+
+// EditEpoch with the device words the edit kernels refuse into (ge_refuse of graph_edit_device.h): the count of
+// refused rows and the packed (sequence, row, status) of the first, {0, ~0} when nothing was refused.
+struct DeviceEditEpoch : EditEpoch {
+    unsigned long long *d_info = nullptr;
+
+    hipError_t reset_async(hipStream_t s)
+    {
+        const hipError_t e = hipMemsetAsync(d_info, 0, sizeof(unsigned long long), s);
+        return e != hipSuccess ? e : hipMemsetAsync(d_info + 1, 0xff, sizeof(unsigned long long), s);
+    }
+
+    // *_get_edit_info, after the caller's wait_last
+    int read_and_reset(StageError &err, int *n_refused, int *first_status)
+    {
+        unsigned long long info[2] = {0, 0};
+        hipError_t e = hipMemcpy(info, d_info, sizeof(info), hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            return err.fail(S2D_EHIP, "hipMemcpy(info, c->d_edit_info, sizeof(info), hipMemcpyDeviceToHost)", e);
+        if (n_refused) *n_refused = (int)info[0];
+        if (first_status) *first_status = info[0] ? -(int)(info[1] & 0xff) : S2D_OK;
+        const unsigned long long fresh[2] = {0, ~0ull};
+        if ((e = hipMemcpy(d_info, fresh, sizeof(fresh), hipMemcpyHostToDevice)) != hipSuccess)
+            return err.fail(S2D_EHIP, "hipMemcpy(c->d_edit_info, fresh, sizeof(fresh), hipMemcpyHostToDevice)", e);
+        seq = 0;
+        return S2D_OK;
+    }
+};
+
+}  // namespace s2d
+#endif  // __HIPCC__

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/slam2d/karto.h"
+#include "knob_int.h"  // parse_knob_int
 
 namespace s2d {
 
@@ -64,18 +65,6 @@ struct KtOptions {
     // context never initialised fails its parity test instead of passing on fresh zero pages
     bool poison = false;
 };
-
-// a knob's whole value as one decimal integer ("12", "-3": no commas, no suffix, not empty) that fits an int.  One
-// out-of-line copy serves every knob of every context (the library has always carried it as a weak symbol).
-__attribute__((noinline)) inline bool parse_knob_int(const char *v, int &out)
-{
-    char *end = nullptr;
-    errno = 0;
-    const long long x = strtoll(v, &end, 10);
-    if (end == v || *end != '\0' || errno != 0 || x < INT_MIN || x > INT_MAX) return false;
-    out = (int)x;
-    return true;
-}
 
 // Every matcher knob, through get (the library: getenv).  Returns NULL, or the message of the refusal: a number
 // that is not one (kt_create then fails with KT_EINVAL).

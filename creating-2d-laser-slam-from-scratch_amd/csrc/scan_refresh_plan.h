@@ -6,7 +6,7 @@
 #pragma once
 #include <limits.h>
 
-#include "karto_internal.h"  // parse_knob_int
+#include "knob_int.h"  // parse_knob_int
 
 namespace s2d {
 

@@ -1,21 +1,24 @@
-// stage_runtime.h -- the host runtime the Karto-family contexts share (kt_, kg_, spa_, kl_, ke_, kp_, kd_, kc_): status
-// codes, the module's error text, stream ordering between calls (DESIGN.md "Streams"), creation helpers, the timing
-// entry points and the device side of the edit epoch.  Host only.  The part above the __HIPCC__ line names no HIP
-// symbol and compiles as plain C++17 (tests/cpp/stage_runtime_check.cpp, with EditEpoch of karto_graph_mirror.h).
+// stage_runtime.h -- the host runtime every context of the library shares (hs_, gm_, pl_, ud_ and the Karto stages
+// kt_, kg_, spa_, kl_, ke_, kp_, kd_, kc_): status codes, the module's error text, stream ordering between calls
+// (DESIGN.md "Streams"), creation helpers and the timing entry points.  Host only, and no family's types.  The part
+// above the __HIPCC__ line names no HIP symbol and compiles as plain C++17 (tests/cpp/stage_runtime_check.cpp).
 #pragma once
 #include <stdlib.h>
 
-#include "karto_internal.h"  // parse_knob_int
+#include "knob_int.h"  // parse_knob_int
 
 namespace s2d {
 
-// The status codes of all eight public headers; each capi file asserts that its own XX_* equal them.
+// The status codes of the public headers; each capi file asserts that its own XX_* equal them.  The four oldest
+// headers (hector.h, gmapping.h, plicp.h, undistort.h) have the first five only: HS_ESTATE is hector.h's own -5.
 enum : int { S2D_OK = 0, S2D_EINVAL = -1, S2D_EHIP = -2, S2D_ENOMEM = -3, S2D_ENODEV = -4, S2D_ERANGE = -5 };
-#define S2D_ASSERT_STATUS_CODES(XX)                                                                          \
+#define S2D_ASSERT_COMMON_CODES(XX)                                                                          \
     static_assert(XX##_OK == s2d::S2D_OK && XX##_EINVAL == s2d::S2D_EINVAL && XX##_EHIP == s2d::S2D_EHIP &&   \
-                      XX##_ENOMEM == s2d::S2D_ENOMEM && XX##_ENODEV == s2d::S2D_ENODEV &&                    \
-                      XX##_ERANGE == s2d::S2D_ERANGE,                                                        \
+                      XX##_ENOMEM == s2d::S2D_ENOMEM && XX##_ENODEV == s2d::S2D_ENODEV,                      \
                   #XX "_* differ from the shared status codes")
+#define S2D_ASSERT_STATUS_CODES(XX) \
+    S2D_ASSERT_COMMON_CODES(XX);    \
+    static_assert(XX##_ERANGE == s2d::S2D_ERANGE, #XX "_ERANGE differs from the shared status code")
 
 // SLAM2D_POISON != 0 (test hook): a context fills its buffers with 0xA5 bytes first.  NULL, or the refusal's text
 // (XX_EINVAL) with `poison` left alone.  Always inlined, so the library exports no symbol for it.
@@ -38,7 +41,6 @@ __attribute__((always_inline)) inline const char *poison_from_env(int &poison)
 #include <vector>
 
 #include "host_timing.h"
-#include "karto_graph_mirror.h"  // EditEpoch
 
 // Nothing below is exported from the library: the types and helpers are the capi files' own.
 namespace s2d __attribute__((visibility("hidden"))) {
@@ -79,6 +81,8 @@ struct StreamOrder {
     hipEvent_t ev_last = nullptr;
     std::mutex mu;
 
+    // a blocking stream (not hipStreamNonBlocking): work a caller queued on the legacy default stream (e.g. torch's
+    // default stream zeroing an output) is ordered before the context's own kernels
     hipError_t create()
     {
         const hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamDefault);
@@ -150,7 +154,8 @@ private:
 };
 
 // Every hipMalloc of a context: the first failure sticks (later calls do nothing), and free_all releases what was
-// allocated, so *_destroy keeps no list of its own.
+// allocated, so *_destroy keeps no list of its own.  A call that allocates after creation reads the failure with
+// take_error and frees what it got, so that a later call can allocate again.
 struct DeviceBuffers {
     std::vector<std::pair<void *, size_t>> owned;
     hipError_t error = hipSuccess;
@@ -163,6 +168,8 @@ struct DeviceBuffers {
         owned.push_back({p, bytes});
         ptr = (T *)p;
     }
+
+    hipError_t take_error() { return std::exchange(error, hipSuccess); }
 
     template <class T>
     void free(T *&ptr)
@@ -210,34 +217,6 @@ inline int get_kernel_times(KernelTimer &timer, StageError &err, double *ms_out,
     S2D_CHK(err, S2D_EHIP, timer.collect(ms_out, launches_out, reset, n));
     return S2D_OK;
 }
-
-// EditEpoch with the device words the edit kernels refuse into (ge_refuse of graph_edit_device.h): the count of
-// refused rows and the packed (sequence, row, status) of the first, {0, ~0} when nothing was refused.
-struct DeviceEditEpoch : EditEpoch {
-    unsigned long long *d_info = nullptr;
-
-    hipError_t reset_async(hipStream_t s)
-    {
-        const hipError_t e = hipMemsetAsync(d_info, 0, sizeof(unsigned long long), s);
-        return e != hipSuccess ? e : hipMemsetAsync(d_info + 1, 0xff, sizeof(unsigned long long), s);
-    }
-
-    // *_get_edit_info, after the caller's wait_last
-    int read_and_reset(StageError &err, int *n_refused, int *first_status)
-    {
-        unsigned long long info[2] = {0, 0};
-        hipError_t e = hipMemcpy(info, d_info, sizeof(info), hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            return err.fail(S2D_EHIP, "hipMemcpy(info, c->d_edit_info, sizeof(info), hipMemcpyDeviceToHost)", e);
-        if (n_refused) *n_refused = (int)info[0];
-        if (first_status) *first_status = info[0] ? -(int)(info[1] & 0xff) : S2D_OK;
-        const unsigned long long fresh[2] = {0, ~0ull};
-        if ((e = hipMemcpy(d_info, fresh, sizeof(fresh), hipMemcpyHostToDevice)) != hipSuccess)
-            return err.fail(S2D_EHIP, "hipMemcpy(c->d_edit_info, fresh, sizeof(fresh), hipMemcpyHostToDevice)", e);
-        seq = 0;
-        return S2D_OK;
-    }
-};
 
 }  // namespace s2d
 #endif  // __HIPCC__

@@ -11,28 +11,14 @@
 #include <vector>
 
 #include "../../include/slam2d/undistort.h"
+#include "stage_runtime.h"
 #include "undistort_kernels.hip"
 
 using namespace s2d;
 
 namespace {
-thread_local std::string ud_err;
-
-int ufail(int code, const char *what, hipError_t e = hipSuccess)
-{
-    ud_err = what;
-    if (e != hipSuccess) {
-        ud_err += ": ";
-        ud_err += hipGetErrorString(e);
-    }
-    return code;
-}
-
-#define UCHK(expr)                                             \
-    do {                                                       \
-        hipError_t _e = (expr);                                \
-        if (_e != hipSuccess) return ufail(UD_EHIP, #expr, _e); \
-    } while (0)
+thread_local StageError ud_err;
+S2D_ASSERT_COMMON_CODES(UD);
 }  // namespace
 
 struct ud_ctx {
@@ -42,6 +28,7 @@ struct ud_ctx {
     double2 *d_cs = nullptr;
     hipStream_t stream = nullptr;
     std::mutex mu;
+    DeviceBuffers mem;
     // single-scan staging (ud_correct)
     float *d_ranges1 = nullptr, *d_cloud1 = nullptr, *d_xy1 = nullptr, *d_origo1 = nullptr;
     double *d_time1 = nullptr, *d_imu1 = nullptr, *d_odom1 = nullptr;
@@ -72,22 +59,22 @@ int launch(ud_ctx *c, int count, const float *d_ranges, int range_stride, const 
                        d_scan_time, d_imu, imu_stride, d_imu_n, d_odom, d_cloud, cloud_stride, (float2 *)d_xy,
                        xy_stride, d_n, (float2 *)d_origo, d_status);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? UD_OK : ufail(UD_EHIP, "ud_correct_kernel launch", e);
+    return e == hipSuccess ? UD_OK : ud_err.fail(UD_EHIP, "ud_correct_kernel launch", e);
 }
 
 int check_batch(ud_ctx *c, int count, const float *d_ranges, int range_stride, const double *d_scan_time,
                 const double *d_imu, int imu_stride, const int *d_imu_n, const double *d_odom, float *d_cloud,
                 int cloud_stride, float *d_xy, int xy_stride, int *d_n)
 {
-    if (!c->has_geometry) return ufail(UD_EINVAL, "ud_set_scan_geometry not called");
-    if (count < 0 || count > c->B) return ufail(UD_EINVAL, "count must be in [0, num_streams]");
+    if (!c->has_geometry) return ud_err.fail(UD_EINVAL, "ud_set_scan_geometry not called");
+    if (count < 0 || count > c->B) return ud_err.fail(UD_EINVAL, "count must be in [0, num_streams]");
     if (count == 0) return UD_OK;
-    if (!d_ranges || !d_scan_time) return ufail(UD_EINVAL, "d_ranges / d_scan_time is NULL");
-    if (range_stride < c->n) return ufail(UD_EINVAL, "range_stride < n_beams");
-    if (c->g.use_imu && (!d_imu || !d_imu_n || imu_stride < 1)) return ufail(UD_EINVAL, "use_imu needs d_imu, d_imu_n, imu_stride >= 1");
-    if (c->g.use_odom && !d_odom) return ufail(UD_EINVAL, "use_odom needs d_odom");
-    if (d_cloud && cloud_stride < c->n) return ufail(UD_EINVAL, "cloud_stride < n_beams");
-    if (d_xy && (!d_n || xy_stride < c->n)) return ufail(UD_EINVAL, "d_xy needs d_n and xy_stride >= n_beams");
+    if (!d_ranges || !d_scan_time) return ud_err.fail(UD_EINVAL, "d_ranges / d_scan_time is NULL");
+    if (range_stride < c->n) return ud_err.fail(UD_EINVAL, "range_stride < n_beams");
+    if (c->g.use_imu && (!d_imu || !d_imu_n || imu_stride < 1)) return ud_err.fail(UD_EINVAL, "use_imu needs d_imu, d_imu_n, imu_stride >= 1");
+    if (c->g.use_odom && !d_odom) return ud_err.fail(UD_EINVAL, "use_odom needs d_odom");
+    if (d_cloud && cloud_stride < c->n) return ud_err.fail(UD_EINVAL, "cloud_stride < n_beams");
+    if (d_xy && (!d_n || xy_stride < c->n)) return ud_err.fail(UD_EINVAL, "d_xy needs d_n and xy_stride >= n_beams");
     return UD_OK;
 }
 }  // namespace
@@ -109,12 +96,11 @@ void ud_default_laser(hs_laser *L, int n_beams, float angle_min, float angle_inc
 
 int ud_create(ud_ctx **out, int num_streams, int n_beams, int max_imu)
 {
-    if (!out) return ufail(UD_EINVAL, "out is NULL");
+    if (!out) return ud_err.fail(UD_EINVAL, "out is NULL");
     *out = nullptr;
-    if (num_streams < 1 || n_beams < 1) return ufail(UD_EINVAL, "need num_streams >= 1, n_beams >= 1");
-    if (max_imu < 1 || max_imu > UD_MAX_IMU) return ufail(UD_EINVAL, "max_imu must be in [1, 2000] (queueLength)");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return ufail(UD_ENODEV, "no HIP device");
+    if (num_streams < 1 || n_beams < 1) return ud_err.fail(UD_EINVAL, "need num_streams >= 1, n_beams >= 1");
+    if (max_imu < 1 || max_imu > UD_MAX_IMU) return ud_err.fail(UD_EINVAL, "max_imu must be in [1, 2000] (queueLength)");
+    if (!device_present()) return ud_err.fail(UD_ENODEV, "no HIP device");
     ud_ctx *c = new ud_ctx;
     c->B = num_streams;
     c->n = n_beams;
@@ -129,20 +115,21 @@ int ud_create(ud_ctx **out, int num_streams, int n_beams, int max_imu)
     hipError_t e;
     if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamDefault)) != hipSuccess) {
         delete c;
-        return ufail(UD_EHIP, "hipStreamCreate", e);
+        return ud_err.fail(UD_EHIP, "hipStreamCreate", e);
     }
     const size_t n = (size_t)n_beams;
-    if ((e = hipMalloc(&c->d_cs, sizeof(double2) * n)) != hipSuccess ||
-        (e = hipMalloc(&c->d_ranges1, sizeof(float) * n)) != hipSuccess ||
-        (e = hipMalloc(&c->d_cloud1, sizeof(float) * 3 * n)) != hipSuccess ||
-        (e = hipMalloc(&c->d_xy1, sizeof(float) * 2 * n)) != hipSuccess ||
-        (e = hipMalloc(&c->d_origo1, sizeof(float) * 2)) != hipSuccess ||
-        (e = hipMalloc(&c->d_time1, sizeof(double) * 2)) != hipSuccess ||
-        (e = hipMalloc(&c->d_imu1, sizeof(double) * 4 * (size_t)max_imu)) != hipSuccess ||
-        (e = hipMalloc(&c->d_odom1, sizeof(double) * 14)) != hipSuccess ||
-        (e = hipMalloc(&c->d_int1, sizeof(int) * 3)) != hipSuccess) {
+    c->mem.alloc(c->d_cs, sizeof(double2) * n);
+    c->mem.alloc(c->d_ranges1, sizeof(float) * n);
+    c->mem.alloc(c->d_cloud1, sizeof(float) * 3 * n);
+    c->mem.alloc(c->d_xy1, sizeof(float) * 2 * n);
+    c->mem.alloc(c->d_origo1, sizeof(float) * 2);
+    c->mem.alloc(c->d_time1, sizeof(double) * 2);
+    c->mem.alloc(c->d_imu1, sizeof(double) * 4 * (size_t)max_imu);
+    c->mem.alloc(c->d_odom1, sizeof(double) * 14);
+    c->mem.alloc(c->d_int1, sizeof(int) * 3);
+    if ((e = c->mem.error) != hipSuccess) {
         ud_destroy(c);
-        return ufail(UD_ENOMEM, "hipMalloc", e);
+        return ud_err.fail(UD_ENOMEM, "hipMalloc", e);
     }
     *out = c;
     return UD_OK;
@@ -152,15 +139,7 @@ int ud_destroy(ud_ctx *c)
 {
     if (!c) return UD_OK;
     if (c->stream) hipStreamSynchronize(c->stream);
-    hipFree(c->d_cs);
-    hipFree(c->d_ranges1);
-    hipFree(c->d_cloud1);
-    hipFree(c->d_xy1);
-    hipFree(c->d_origo1);
-    hipFree(c->d_time1);
-    hipFree(c->d_imu1);
-    hipFree(c->d_odom1);
-    hipFree(c->d_int1);
+    c->mem.free_all();
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
     return UD_OK;
@@ -169,7 +148,7 @@ int ud_destroy(ud_ctx *c)
 int ud_set_scan_geometry(ud_ctx *c, float angle_min, float angle_increment, float range_min, float range_max,
                          const double *unit_vectors)
 {
-    if (!c) return ufail(UD_EINVAL, "ctx is NULL");
+    if (!c) return ud_err.fail(UD_EINVAL, "ctx is NULL");
     std::lock_guard<std::mutex> lock(c->mu);
     std::vector<double> cs((size_t)2 * c->n);
     for (int i = 0; i < c->n; ++i) {
@@ -183,8 +162,8 @@ int ud_set_scan_geometry(ud_ctx *c, float angle_min, float angle_increment, floa
             cs[2 * i + 1] = sin(angle);
         }
     }
-    UCHK(hipMemcpyAsync(c->d_cs, cs.data(), sizeof(double) * cs.size(), hipMemcpyHostToDevice, c->stream));
-    UCHK(hipStreamSynchronize(c->stream));
+    S2D_CHK(ud_err, UD_EHIP, hipMemcpyAsync(c->d_cs, cs.data(), sizeof(double) * cs.size(), hipMemcpyHostToDevice, c->stream));
+    S2D_CHK(ud_err, UD_EHIP, hipStreamSynchronize(c->stream));
     c->g.range_min = range_min;
     c->g.range_max = range_max;
     c->has_geometry = true;
@@ -193,7 +172,7 @@ int ud_set_scan_geometry(ud_ctx *c, float angle_min, float angle_increment, floa
 
 int ud_set_container_rules(ud_ctx *c, const hs_laser *L, float scale_to_map)
 {
-    if (!c || !L) return ufail(UD_EINVAL, "NULL argument");
+    if (!c || !L) return ud_err.fail(UD_EINVAL, "NULL argument");
     std::lock_guard<std::mutex> lock(c->mu);
     set_rules(c, L, scale_to_map);
     return UD_OK;
@@ -201,7 +180,7 @@ int ud_set_container_rules(ud_ctx *c, const hs_laser *L, float scale_to_map)
 
 int ud_set_sources(ud_ctx *c, int use_imu, int use_odom)
 {
-    if (!c) return ufail(UD_EINVAL, "ctx is NULL");
+    if (!c) return ud_err.fail(UD_EINVAL, "ctx is NULL");
     std::lock_guard<std::mutex> lock(c->mu);
     c->g.use_imu = use_imu != 0;
     c->g.use_odom = use_odom != 0;
@@ -213,7 +192,7 @@ int ud_correct_batch_device(ud_ctx *c, int count, const float *d_ranges, int ran
                             float *d_cloud, int cloud_stride, float *d_xy, int xy_stride, int *d_n, float *d_origo,
                             int *d_status, void *hip_stream)
 {
-    if (!c) return ufail(UD_EINVAL, "ctx is NULL");
+    if (!c) return ud_err.fail(UD_EINVAL, "ctx is NULL");
     std::lock_guard<std::mutex> lock(c->mu);
     int rc = check_batch(c, count, d_ranges, range_stride, d_scan_time, d_imu, imu_stride, d_imu_n, d_odom, d_cloud,
                          cloud_stride, d_xy, xy_stride, d_n);
@@ -227,36 +206,36 @@ int ud_correct(ud_ctx *c, const float *ranges, double scan_time_start, double sc
                int imu_n, const double *odom, float *cloud_out, float *xy_out, int *n_out, float *origo_out,
                int *status_out)
 {
-    if (!c || !ranges) return ufail(UD_EINVAL, "NULL argument");
+    if (!c || !ranges) return ud_err.fail(UD_EINVAL, "NULL argument");
     std::lock_guard<std::mutex> lock(c->mu);
-    if (!c->has_geometry) return ufail(UD_EINVAL, "ud_set_scan_geometry not called");
+    if (!c->has_geometry) return ud_err.fail(UD_EINVAL, "ud_set_scan_geometry not called");
     if (c->g.use_imu) {
-        if (imu_n < 0 || imu_n > c->max_imu) return ufail(UD_EINVAL, "imu_n must be in [0, max_imu]");
-        if (imu_n > 0 && !imu) return ufail(UD_EINVAL, "imu is NULL");
+        if (imu_n < 0 || imu_n > c->max_imu) return ud_err.fail(UD_EINVAL, "imu_n must be in [0, max_imu]");
+        if (imu_n > 0 && !imu) return ud_err.fail(UD_EINVAL, "imu is NULL");
         for (int i = 1; i < imu_n; ++i)
-            if (!(imu[4 * i] >= imu[4 * (i - 1)])) return ufail(UD_EINVAL, "IMU times must be non-decreasing");
+            if (!(imu[4 * i] >= imu[4 * (i - 1)])) return ud_err.fail(UD_EINVAL, "IMU times must be non-decreasing");
     } else {
         imu_n = 0;
     }
-    if (c->g.use_odom && !odom) return ufail(UD_EINVAL, "odom is NULL");
+    if (c->g.use_odom && !odom) return ud_err.fail(UD_EINVAL, "odom is NULL");
     hipStream_t s = c->stream;
     const double tm[2] = {scan_time_start, scan_time_increment};
     const int n = c->n;
-    UCHK(hipMemcpyAsync(c->d_ranges1, ranges, sizeof(float) * n, hipMemcpyHostToDevice, s));
-    UCHK(hipMemcpyAsync(c->d_time1, tm, sizeof(tm), hipMemcpyHostToDevice, s));
-    if (imu_n > 0) UCHK(hipMemcpyAsync(c->d_imu1, imu, sizeof(double) * 4 * imu_n, hipMemcpyHostToDevice, s));
-    UCHK(hipMemcpyAsync(c->d_int1, &imu_n, sizeof(int), hipMemcpyHostToDevice, s));
-    if (c->g.use_odom) UCHK(hipMemcpyAsync(c->d_odom1, odom, sizeof(double) * 14, hipMemcpyHostToDevice, s));
-    UCHK(hipStreamSynchronize(s));  // the sources are pageable host memory of the caller
+    S2D_CHK(ud_err, UD_EHIP, hipMemcpyAsync(c->d_ranges1, ranges, sizeof(float) * n, hipMemcpyHostToDevice, s));
+    S2D_CHK(ud_err, UD_EHIP, hipMemcpyAsync(c->d_time1, tm, sizeof(tm), hipMemcpyHostToDevice, s));
+    if (imu_n > 0) S2D_CHK(ud_err, UD_EHIP, hipMemcpyAsync(c->d_imu1, imu, sizeof(double) * 4 * imu_n, hipMemcpyHostToDevice, s));
+    S2D_CHK(ud_err, UD_EHIP, hipMemcpyAsync(c->d_int1, &imu_n, sizeof(int), hipMemcpyHostToDevice, s));
+    if (c->g.use_odom) S2D_CHK(ud_err, UD_EHIP, hipMemcpyAsync(c->d_odom1, odom, sizeof(double) * 14, hipMemcpyHostToDevice, s));
+    S2D_CHK(ud_err, UD_EHIP, hipStreamSynchronize(s));  // the sources are pageable host memory of the caller
     int rc = launch(c, 1, c->d_ranges1, n, c->d_time1, c->d_imu1, c->max_imu, c->d_int1, c->d_odom1, c->d_cloud1, n,
                     c->d_xy1, n, c->d_int1 + 1, c->d_origo1, c->d_int1 + 2, s);
     if (rc != UD_OK) return rc;
     int res[3] = {0, 0, 0};
-    UCHK(hipMemcpyAsync(res, c->d_int1, sizeof(res), hipMemcpyDeviceToHost, s));
-    UCHK(hipStreamSynchronize(s));
-    if (cloud_out) UCHK(hipMemcpy(cloud_out, c->d_cloud1, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
-    if (xy_out && res[1] > 0) UCHK(hipMemcpy(xy_out, c->d_xy1, sizeof(float) * 2 * res[1], hipMemcpyDeviceToHost));
-    if (origo_out) UCHK(hipMemcpy(origo_out, c->d_origo1, sizeof(float) * 2, hipMemcpyDeviceToHost));
+    S2D_CHK(ud_err, UD_EHIP, hipMemcpyAsync(res, c->d_int1, sizeof(res), hipMemcpyDeviceToHost, s));
+    S2D_CHK(ud_err, UD_EHIP, hipStreamSynchronize(s));
+    if (cloud_out) S2D_CHK(ud_err, UD_EHIP, hipMemcpy(cloud_out, c->d_cloud1, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
+    if (xy_out && res[1] > 0) S2D_CHK(ud_err, UD_EHIP, hipMemcpy(xy_out, c->d_xy1, sizeof(float) * 2 * res[1], hipMemcpyDeviceToHost));
+    if (origo_out) S2D_CHK(ud_err, UD_EHIP, hipMemcpy(origo_out, c->d_origo1, sizeof(float) * 2, hipMemcpyDeviceToHost));
     if (n_out) *n_out = res[1];
     if (status_out) *status_out = res[2];
     return UD_OK;
@@ -264,11 +243,11 @@ int ud_correct(ud_ctx *c, const float *ranges, double scan_time_start, double sc
 
 int ud_rpy_from_quaternion(const double q[4], double rpy[3])
 {
-    if (!q || !rpy) return ufail(UD_EINVAL, "NULL argument");
+    if (!q || !rpy) return ud_err.fail(UD_EINVAL, "NULL argument");
     // tf::Matrix3x3::setRotation(q)
     const double x = q[0], y = q[1], z = q[2], w = q[3];
     const double d = x * x + y * y + z * z + w * w;
-    if (!(d != 0.0)) return ufail(UD_EINVAL, "zero quaternion");
+    if (!(d != 0.0)) return ud_err.fail(UD_EINVAL, "zero quaternion");
     const double s = 2.0 / d;
     const double xs = x * s, ys = y * s, zs = z * s;
     const double wx = w * xs, wy = w * ys, wz = w * zs;

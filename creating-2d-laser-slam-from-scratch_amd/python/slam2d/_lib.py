@@ -114,12 +114,6 @@ def lib() -> C.CDLL:
     return _LIB
 
 
-def check(rc: int, what: str = "") -> None:
-    if rc != 0:
-        msg = lib().hs_last_error().decode(errors="replace")
-        raise Slam2dError(f"{what} failed with code {rc}: {msg}")
-
-
 def source_id_of_tree() -> str:
     """16 hex digits of sha256 over the Hector kernel sources in csrc/ (the Makefile's SRC_HASH)."""
     import hashlib

@@ -1,6 +1,6 @@
-"""What the wrappers of the Karto-family contexts share (karto.py, karto_grid.py, spa.py, karto_loop.py, karto_link.py,
-karto_process.py, karto_edit.py, karto_correct.py): the error check, the context's lifetime, the kernel timing calls and the ctypes
-helpers.  A subclass names its C prefix (`_PREFIX = "kl"`), sets `self.L` and `self.h`, and mirrors its entry points.
+"""What the wrappers of every context share (hector.py, gmapping.py, plicp.py, undistort.py and the Karto stages'): the
+error check, the context's lifetime, the kernel timing calls and the ctypes helpers.  A subclass names its C prefix
+(`_PREFIX = "kl"`), sets `self.L` and `self.h`, and mirrors its entry points.
 """
 from __future__ import annotations
 
@@ -61,7 +61,8 @@ class Stage:
 
 class TimedStage(Stage):
     """A stage with the xx_set_timing / xx_num_kernels / xx_kernel_name / xx_get_kernel_times calls.  The two oldest
-    wrappers override both methods only to keep their signatures (`on`, reset=True)."""
+    wrappers override both methods only to keep their signatures (`on`, reset=True); hector.py, gmapping.py and plicp.py,
+    whose C-ABI has no kernel-name calls, keep their own pair on `Stage`."""
 
     def set_timing(self, enable: bool):
         p = self._PREFIX

@@ -14,15 +14,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import Slam2dError
-
-
-def _fp(a: np.ndarray):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def _check(L, rc: int, what: str):
-    if rc != 0:
-        raise Slam2dError(f"{what} failed with code {rc}: {L.gm_last_error().decode(errors='replace')}")
+from ._stage import Stage
+from ._stage import hp as _fp
 
 
 # gmapping.cc ctor defaults / launch parameters: +-40 m map at 0.05 m,
@@ -30,8 +23,10 @@ def _check(L, rc: int, what: str):
 DEFAULTS = dict(xmin=-40.0, ymin=-40.0, xmax=40.0, ymax=40.0, delta=0.05, max_range=30.0 - 0.01, max_urange=25.0)
 
 
-class GMappingFleet:
+class GMappingFleet(Stage):
     """P particle maps of GMapping::ComputeMap on one GPU."""
+
+    _PREFIX = "gm"
 
     def __init__(self, num_particles: int, max_beams: int = 1081, **params):
         p = dict(DEFAULTS)
@@ -39,26 +34,15 @@ class GMappingFleet:
         self.L = _lib.lib()
         self.P = num_particles
         self.h = C.c_void_p()
-        _check(self.L, self.L.gm_create(C.byref(self.h), num_particles, max_beams, p["xmin"], p["ymin"], p["xmax"],
-                                        p["ymax"], p["delta"], p["max_range"], p["max_urange"]), "gm_create")
+        self._check(self.L.gm_create(C.byref(self.h), num_particles, max_beams, p["xmin"], p["ymin"], p["xmax"],
+                                     p["ymax"], p["delta"], p["max_range"], p["max_urange"]), "gm_create")
         sx, sy = C.c_int(), C.c_int()
         self.L.gm_get_map_size(self.h, C.byref(sx), C.byref(sy))
         self.size = (sx.value, sy.value)
         self.n_beams = 0
 
-    def close(self):
-        if self.h:
-            self.L.gm_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def reset(self):
-        _check(self.L, self.L.gm_reset(self.h), "gm_reset")
+        self._check(self.L.gm_reset(self.h), "gm_reset")
 
     def set_beams(self, angles=None, a_cos=None, a_sin=None):
         """GMapping::CreateCache (gmapping.cc:111-124): cos/sin of every beam angle (double)."""
@@ -67,11 +51,11 @@ class GMappingFleet:
             a_cos, a_sin = np.cos(angles), np.sin(angles)
         a_cos = np.ascontiguousarray(a_cos, np.float64)
         a_sin = np.ascontiguousarray(a_sin, np.float64)
-        _check(self.L, self.L.gm_set_beams(self.h, _fp(a_cos), _fp(a_sin), a_cos.shape[0]), "gm_set_beams")
+        self._check(self.L.gm_set_beams(self.h, _fp(a_cos), _fp(a_sin), a_cos.shape[0]), "gm_set_beams")
         self.n_beams = a_cos.shape[0]
 
     def set_occ_thresh(self, t: float):
-        _check(self.L, self.L.gm_set_occ_thresh(self.h, float(t)), "gm_set_occ_thresh")
+        self._check(self.L.gm_set_occ_thresh(self.h, float(t)), "gm_set_occ_thresh")
 
     @staticmethod
     def poses4(poses_xyt) -> np.ndarray:
@@ -83,54 +67,53 @@ class GMappingFleet:
         """ComputeMap for every particle (host arrays, synchronous)."""
         poses4 = np.ascontiguousarray(poses4, np.float64).reshape(self.P, 4)
         ranges = np.ascontiguousarray(ranges, np.float32)
-        _check(self.L, self.L.gm_compute_maps(self.h, _fp(poses4), _fp(ranges), ranges.shape[0]), "gm_compute_maps")
+        self._check(self.L.gm_compute_maps(self.h, _fp(poses4), _fp(ranges), ranges.shape[0]), "gm_compute_maps")
 
     def compute_device(self, d_poses4: int, d_ranges: int, n: int, d_scores: int = 0, begin: int = 0,
                        count: int | None = None, hip_stream: int = 0):
         count = self.P - begin if count is None else count
-        _check(self.L, self.L.gm_compute_maps_device(self.h, begin, count, C.c_void_p(d_poses4), C.c_void_p(d_ranges),
-                                                     int(n), C.c_void_p(d_scores or None),
-                                                     C.c_void_p(hip_stream or None)), "gm_compute_maps_device")
+        self._check(self.L.gm_compute_maps_device(self.h, begin, count, C.c_void_p(d_poses4), C.c_void_p(d_ranges),
+                                                  int(n), C.c_void_p(d_scores or None), C.c_void_p(hip_stream or None)),
+                    "gm_compute_maps_device")
 
     def normalize_weights_device(self, comm, d_scores: int, count: int, d_weights: int, d_sums: int,
                                  hip_stream: int = 0):
         """gm_normalize_weights_device: [Σ(s+1), Σ(s+1)^2] of this rank's scores all-reduced with RCCL on
         `comm` (an RcclComm or None for a single rank), weights (double[count]) and sums (double[2])."""
-        _check(self.L, self.L.gm_normalize_weights_device(self.h, C.c_void_p(comm.handle if comm else None),
-                                                          C.c_void_p(d_scores), int(count),
-                                                          C.c_void_p(d_weights or None), C.c_void_p(d_sums),
-                                                          C.c_void_p(hip_stream or None)),
-               "gm_normalize_weights_device")
+        self._check(self.L.gm_normalize_weights_device(self.h, C.c_void_p(comm.handle if comm else None),
+                                                       C.c_void_p(d_scores), int(count), C.c_void_p(d_weights or None),
+                                                       C.c_void_p(d_sums), C.c_void_p(hip_stream or None)),
+                    "gm_normalize_weights_device")
 
     def particle_map(self, p: int):
         sx, sy = self.size
         n = np.empty(sx * sy, np.int32)
         v = np.empty(sx * sy, np.int32)
         acc = np.empty(2 * sx * sy, np.float32)
-        _check(self.L, self.L.gm_get_particle_map(self.h, p, _fp(n), _fp(v), _fp(acc)), "gm_get_particle_map")
+        self._check(self.L.gm_get_particle_map(self.h, p, _fp(n), _fp(v), _fp(acc)), "gm_get_particle_map")
         return n.reshape(sy, sx), v.reshape(sy, sx), acc.reshape(sy, sx, 2)
 
     def publish(self, p: int) -> np.ndarray:
         sx, sy = self.size
         o = np.empty(sx * sy, np.int8)
-        _check(self.L, self.L.gm_publish(self.h, p, _fp(o)), "gm_publish")
+        self._check(self.L.gm_publish(self.h, p, _fp(o)), "gm_publish")
         return o.reshape(sy, sx)
 
     def scores(self):
         s = np.empty(self.P, np.int32)
         h = np.empty(self.P, np.int32)
         f = np.empty(self.P, np.int64)
-        _check(self.L, self.L.gm_get_scores(self.h, _fp(s), _fp(h), _fp(f)), "gm_get_scores")
+        self._check(self.L.gm_get_scores(self.h, _fp(s), _fp(h), _fp(f)), "gm_get_scores")
         return s, h, f
 
     def set_timing(self, on: bool):
-        _check(self.L, self.L.gm_set_timing(self.h, 1 if on else 0), "gm_set_timing")
+        self._check(self.L.gm_set_timing(self.h, 1 if on else 0), "gm_set_timing")
 
     def kernel_times(self, reset=True):
         ms = C.c_double()
         n = C.c_int64()
-        _check(self.L, self.L.gm_get_kernel_times(self.h, C.byref(ms), C.byref(n), 1 if reset else 0),
-               "gm_get_kernel_times")
+        self._check(self.L.gm_get_kernel_times(self.h, C.byref(ms), C.byref(n), 1 if reset else 0),
+                    "gm_get_kernel_times")
         return ms.value, n.value
 
 

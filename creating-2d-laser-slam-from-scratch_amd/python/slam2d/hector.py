@@ -16,13 +16,10 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check
+from ._stage import Stage
+from ._stage import hp as _fp
 
 _f = C.c_float
-
-
-def _fp(a: np.ndarray):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 class DataContainer:
@@ -100,8 +97,10 @@ class HsLaser(C.Structure):
                 "z_min": self.laser_z_min_value, "z_max": self.laser_z_max_value}
 
 
-class HectorFleet:
+class HectorFleet(Stage):
     """B independent Hector SLAM streams resident in HBM (one MapRepMultiMap pyramid each)."""
+
+    _PREFIX = "hs"
 
     def __init__(self, num_streams=1, map_resolution=0.05, map_size=2048, map_start=(0.5, 0.5), levels=3,
                  max_points=1081, map_size_y=None):
@@ -111,40 +110,30 @@ class HectorFleet:
         self.max_points = int(max_points)
         h = C.c_void_p()
         sy = map_size if map_size_y is None else map_size_y
-        check(self.L.hs_create(C.byref(h), self.B, _f(map_resolution), int(map_size), int(sy), _f(map_start[0]),
-                               _f(map_start[1]), self.levels, self.max_points), "hs_create")
+        self._check(self.L.hs_create(C.byref(h), self.B, _f(map_resolution), int(map_size), int(sy), _f(map_start[0]),
+                                     _f(map_start[1]), self.levels, self.max_points), "hs_create")
         self.h = h
 
-    # ---------------------------------------------------------------- lifecycle
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.hs_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
+    # ---------------------------------------------------------------- lifecycle (close, __del__: Stage)
     def reset(self):
-        check(self.L.hs_reset(self.h), "hs_reset")
+        self._check(self.L.hs_reset(self.h), "hs_reset")
 
     def set_update_factors(self, free_factor: float, occupied_factor: float):
-        check(self.L.hs_set_update_factors(self.h, _f(free_factor), _f(occupied_factor)), "hs_set_update_factors")
+        self._check(self.L.hs_set_update_factors(self.h, _f(free_factor), _f(occupied_factor)), "hs_set_update_factors")
 
     def set_thresholds(self, min_dist: float, min_angle: float):
-        check(self.L.hs_set_map_update_thresholds(self.h, _f(min_dist), _f(min_angle)), "hs_set_map_update_thresholds")
+        self._check(self.L.hs_set_map_update_thresholds(self.h, _f(min_dist), _f(min_angle)),
+                    "hs_set_map_update_thresholds")
 
     ORDER_REFERENCE = 0   # H / b summed in point order, as OccGridMapUtil.h:94-126 (default)
     ORDER_TREE256 = 256   # 256-thread tree (faster; the oracle's reduce_threads=256)
 
     def set_reduction_order(self, order: int):
-        check(self.L.hs_set_reduction_order(self.h, int(order)), "hs_set_reduction_order")
+        self._check(self.L.hs_set_reduction_order(self.h, int(order)), "hs_set_reduction_order")
 
     def reduction_order(self) -> int:
         o = C.c_int()
-        check(self.L.hs_get_reduction_order(self.h, C.byref(o)), "hs_get_reduction_order")
+        self._check(self.L.hs_get_reduction_order(self.h, C.byref(o)), "hs_get_reduction_order")
         return o.value
 
     # ---------------------------------------------------------------- single-stream (host buffers)
@@ -157,8 +146,8 @@ class HectorFleet:
         if hint is not None:
             hint = np.ascontiguousarray(hint, np.float32)
             hp = _fp(hint)
-        check(self.L.hs_update(self.h, stream, _fp(pts), pts.shape[0], _f(origo[0]), _f(origo[1]), hp,
-                               1 if map_without_matching else 0, _fp(pose), _fp(cov), C.byref(did)), "hs_update")
+        self._check(self.L.hs_update(self.h, stream, _fp(pts), pts.shape[0], _f(origo[0]), _f(origo[1]), hp,
+                                     1 if map_without_matching else 0, _fp(pose), _fp(cov), C.byref(did)), "hs_update")
         return pose, cov.reshape(3, 3), bool(did.value)
 
     def match(self, stream: int, pts, hint, origo=(0.0, 0.0)):
@@ -166,37 +155,38 @@ class HectorFleet:
         hint = np.ascontiguousarray(hint, np.float32)
         pose = np.zeros(3, np.float32)
         cov = np.zeros(9, np.float32)
-        check(self.L.hs_match(self.h, stream, _fp(pts), pts.shape[0], _f(origo[0]), _f(origo[1]), _fp(hint),
-                              _fp(pose), _fp(cov)), "hs_match")
+        self._check(self.L.hs_match(self.h, stream, _fp(pts), pts.shape[0], _f(origo[0]), _f(origo[1]), _fp(hint),
+                                    _fp(pose), _fp(cov)), "hs_match")
         return pose, cov.reshape(3, 3)
 
     def update_by_scan(self, stream: int, pts, pose, origo=(0.0, 0.0)):
         pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
         pose = np.ascontiguousarray(pose, np.float32)
-        check(self.L.hs_update_by_scan(self.h, stream, _fp(pts), pts.shape[0], _f(origo[0]), _f(origo[1]),
-                                       _fp(pose)), "hs_update_by_scan")
+        self._check(self.L.hs_update_by_scan(self.h, stream, _fp(pts), pts.shape[0], _f(origo[0]), _f(origo[1]),
+                                             _fp(pose)), "hs_update_by_scan")
 
     def last_pose(self, stream: int = 0):
         pose = np.zeros(3, np.float32)
         cov = np.zeros(9, np.float32)
-        check(self.L.hs_get_last_pose(self.h, stream, _fp(pose), _fp(cov)), "hs_get_last_pose")
+        self._check(self.L.hs_get_last_pose(self.h, stream, _fp(pose), _fp(cov)), "hs_get_last_pose")
         return pose, cov.reshape(3, 3)
 
     def clamp_count(self, stream: int = 0) -> int:
         """Gauss-Newton steps of the stream whose rotation update was cut to +-0.2 rad (hs_get_clamp_count)."""
         n = C.c_int()
-        check(self.L.hs_get_clamp_count(self.h, stream, C.byref(n)), "hs_get_clamp_count")
+        self._check(self.L.hs_get_clamp_count(self.h, stream, C.byref(n)), "hs_get_clamp_count")
         return n.value
 
     def map_info(self, level: int = 0):
         sx, sy, cl = C.c_int(), C.c_int(), C.c_float()
         org = np.zeros(2, np.float32)
-        check(self.L.hs_get_map_info(self.h, level, C.byref(sx), C.byref(sy), C.byref(cl), _fp(org)), "hs_get_map_info")
+        self._check(self.L.hs_get_map_info(self.h, level, C.byref(sx), C.byref(sy), C.byref(cl), _fp(org)),
+                    "hs_get_map_info")
         return sx.value, sy.value, cl.value, org
 
     def scale_to_map(self) -> float:
         s = C.c_float()
-        check(self.L.hs_get_scale_to_map(self.h, C.byref(s)), "hs_get_scale_to_map")
+        self._check(self.L.hs_get_scale_to_map(self.h, C.byref(s)), "hs_get_scale_to_map")
         return s.value
 
     def get_map(self, stream: int = 0, level: int = 0, want_occ=True, want_raw=True):
@@ -205,8 +195,9 @@ class HectorFleet:
         l = np.empty(sx * sy, np.float32) if want_raw else None
         u = np.empty(sx * sy, np.int32) if want_raw else None
         ui = C.c_int()
-        check(self.L.hs_get_map(self.h, stream, level, _fp(occ) if want_occ else None, _fp(l) if want_raw else None,
-                                _fp(u) if want_raw else None, C.byref(ui)), "hs_get_map")
+        self._check(self.L.hs_get_map(self.h, stream, level, _fp(occ) if want_occ else None,
+                                      _fp(l) if want_raw else None, _fp(u) if want_raw else None, C.byref(ui)),
+                    "hs_get_map")
         r = {"update_index": ui.value}
         if want_occ:
             r["occ"] = occ.reshape(sy, sx)
@@ -218,27 +209,28 @@ class HectorFleet:
     def flush_ordinals(self, hip_stream: int = 0):
         """hs_flush_ordinals: every stream's 16-bit update ordinals into the int32 updateIndex plane now (zero-copy
         readers of hs_get_device_buffers; replayed graph captures of *_device calls, at least every 32000 steps)."""
-        check(self.L.hs_flush_ordinals(self.h, C.c_void_p(hip_stream or None)), "hs_flush_ordinals")
+        self._check(self.L.hs_flush_ordinals(self.h, C.c_void_p(hip_stream or None)), "hs_flush_ordinals")
 
     def device_cells(self):
         """(device pointer, bytes, stream_words) of the tiled cell storage (hs_get_device_buffers)."""
         p, nb, sw = C.c_void_p(), C.c_size_t(), C.c_size_t()
-        check(self.L.hs_get_device_buffers(self.h, C.byref(p), C.byref(nb), C.byref(sw)), "hs_get_device_buffers")
+        self._check(self.L.hs_get_device_buffers(self.h, C.byref(p), C.byref(nb), C.byref(sw)), "hs_get_device_buffers")
         return p.value, nb.value, sw.value
 
     def set_map(self, stream: int, level: int, logodds, upd):
         l = np.ascontiguousarray(logodds, np.float32)
         u = np.ascontiguousarray(upd, np.int32)
-        check(self.L.hs_set_map(self.h, stream, level, _fp(l), _fp(u)), "hs_set_map")
+        self._check(self.L.hs_set_map(self.h, stream, level, _fp(l), _fp(u)), "hs_set_map")
 
     # ---------------------------------------------------------------- batched device path
     def step_device(self, d_xy: int, xy_stride: int, d_n: int, d_origo: int = 0, d_hints: int = 0,
                     stream_begin: int = 0, count: int | None = None, hip_stream: int = 0):
         """One HectorSlamProcessor::update for every stream; pointers are device addresses (ints)."""
         count = self.B - stream_begin if count is None else count
-        check(self.L.hs_step_batch_device(self.h, stream_begin, count, C.c_void_p(d_xy), int(xy_stride),
-                                          C.c_void_p(d_n), C.c_void_p(d_origo or None), C.c_void_p(d_hints or None),
-                                          C.c_void_p(hip_stream or None)), "hs_step_batch_device")
+        self._check(self.L.hs_step_batch_device(self.h, stream_begin, count, C.c_void_p(d_xy), int(xy_stride),
+                                                C.c_void_p(d_n), C.c_void_p(d_origo or None),
+                                                C.c_void_p(d_hints or None), C.c_void_p(hip_stream or None)),
+                    "hs_step_batch_device")
 
     # ---- scan ingest (LaserScan -> DataContainer on the device), hector_slam.cc:186-198, 320-362 ----
     def set_laser(self, laser: "HsLaser", unit_vectors=None):
@@ -247,27 +239,29 @@ class HectorFleet:
         uv = None
         if unit_vectors is not None:
             uv = np.ascontiguousarray(unit_vectors, np.float64).reshape(-1)
-        check(self.L.hs_set_laser(self.h, C.byref(laser), _fp(uv) if uv is not None else None), "hs_set_laser")
+        self._check(self.L.hs_set_laser(self.h, C.byref(laser), _fp(uv) if uv is not None else None), "hs_set_laser")
 
     def ingest_device(self, count: int, d_ranges: int, range_stride: int, d_xy: int, xy_stride: int, d_n: int,
                       d_origo: int = 0, hip_stream: int = 0):
-        check(self.L.hs_ingest_batch_device(self.h, count, C.c_void_p(d_ranges), int(range_stride), C.c_void_p(d_xy),
-                                            int(xy_stride), C.c_void_p(d_n), C.c_void_p(d_origo or None),
-                                            C.c_void_p(hip_stream or None)), "hs_ingest_batch_device")
+        self._check(self.L.hs_ingest_batch_device(self.h, count, C.c_void_p(d_ranges), int(range_stride),
+                                                  C.c_void_p(d_xy), int(xy_stride), C.c_void_p(d_n),
+                                                  C.c_void_p(d_origo or None), C.c_void_p(hip_stream or None)),
+                    "hs_ingest_batch_device")
 
     def step_ranges_device(self, d_ranges: int, range_stride: int, d_hints: int = 0, stream_begin: int = 0,
                            count: int | None = None, hip_stream: int = 0):
         """scanCallback for every stream: ingest + HectorSlamProcessor::update (device pointers)."""
         count = self.B - stream_begin if count is None else count
-        check(self.L.hs_step_ranges_batch_device(self.h, stream_begin, count, C.c_void_p(d_ranges), int(range_stride),
-                                                 C.c_void_p(d_hints or None), C.c_void_p(hip_stream or None)),
-              "hs_step_ranges_batch_device")
+        self._check(self.L.hs_step_ranges_batch_device(self.h, stream_begin, count, C.c_void_p(d_ranges),
+                                                       int(range_stride), C.c_void_p(d_hints or None),
+                                                       C.c_void_p(hip_stream or None)), "hs_step_ranges_batch_device")
 
     def run_ranges_device(self, steps: int, d_ranges: int, range_stride: int, step_stride: int, hip_stream: int = 0):
         """scanCallback for `steps` consecutive scans of every stream (step k at d_ranges + k * step_stride
         floats); two fleet halves pipelined on two HIP streams, joined on hip_stream."""
-        check(self.L.hs_run_ranges_device(self.h, int(steps), C.c_void_p(d_ranges), int(range_stride),
-                                          int(step_stride), C.c_void_p(hip_stream or None)), "hs_run_ranges_device")
+        self._check(self.L.hs_run_ranges_device(self.h, int(steps), C.c_void_p(d_ranges), int(range_stride),
+                                                int(step_stride), C.c_void_p(hip_stream or None)),
+                    "hs_run_ranges_device")
 
     def update_ranges(self, stream: int, ranges):
         """scanCallback for one stream from host ranges (float32 [n_beams])."""
@@ -275,7 +269,8 @@ class HectorFleet:
         pose = np.zeros(3, np.float32)
         cov = np.zeros(9, np.float32)
         did = C.c_int()
-        check(self.L.hs_update_ranges(self.h, stream, _fp(r), _fp(pose), _fp(cov), C.byref(did)), "hs_update_ranges")
+        self._check(self.L.hs_update_ranges(self.h, stream, _fp(r), _fp(pose), _fp(cov), C.byref(did)),
+                    "hs_update_ranges")
         return pose, cov.reshape(3, 3), bool(did.value)
 
     def poses(self):
@@ -283,57 +278,59 @@ class HectorFleet:
         cv = np.zeros((self.B, 9), np.float32)
         d = np.zeros(self.B, np.int32)
         cells = np.zeros(self.B, np.int64)
-        check(self.L.hs_get_poses(self.h, _fp(p), _fp(cv), _fp(d), _fp(cells)), "hs_get_poses")
+        self._check(self.L.hs_get_poses(self.h, _fp(p), _fp(cv), _fp(d), _fp(cells)), "hs_get_poses")
         return p, cv.reshape(self.B, 3, 3), d.astype(bool), cells
 
     def counters(self, reset=True):
         o = np.zeros(6, np.int64)
-        check(self.L.hs_get_counters(self.h, _fp(o), 1 if reset else 0), "hs_get_counters")
+        self._check(self.L.hs_get_counters(self.h, _fp(o), 1 if reset else 0), "hs_get_counters")
         return {"cells": int(o[0]), "rays": int(o[1]), "gn_points": int(o[2]), "updates": int(o[3]), "steps": int(o[4]),
                 "touched": int(o[5])}
 
     def set_pose_log(self, d_buf: int, streams: int, capacity: int):
         """Device pose log (float32 [capacity][streams][3]) filled by every step; d_buf = 0 disables."""
-        check(self.L.hs_set_pose_log(self.h, C.c_void_p(d_buf or None), int(streams), int(capacity)), "hs_set_pose_log")
+        self._check(self.L.hs_set_pose_log(self.h, C.c_void_p(d_buf or None), int(streams), int(capacity)),
+                    "hs_set_pose_log")
 
     def set_pose_log_slots(self, d_buf: int, d_slot_of_stream: int, slots: int, capacity: int):
         """Device pose log of any subset of streams: stream s -> slot d_slot_of_stream[s] (< 0: not logged)."""
-        check(self.L.hs_set_pose_log_slots(self.h, C.c_void_p(d_buf or None), C.c_void_p(d_slot_of_stream or None),
-                                           int(slots), int(capacity)), "hs_set_pose_log_slots")
+        self._check(self.L.hs_set_pose_log_slots(self.h, C.c_void_p(d_buf or None),
+                                                 C.c_void_p(d_slot_of_stream or None), int(slots), int(capacity)),
+                    "hs_set_pose_log_slots")
 
     def queue_stats(self, reset_stamps=True):
         o = np.zeros(8, np.int64)
-        check(self.L.hs_get_queue_stats(self.h, _fp(o), 1 if reset_stamps else 0), "hs_get_queue_stats")
+        self._check(self.L.hs_get_queue_stats(self.h, _fp(o), 1 if reset_stamps else 0), "hs_get_queue_stats")
         return {"items": int(o[0]), "segments": int(o[1]), "whole": int(o[2]), "overflow": int(o[3]),
                 "cyc_setup": int(o[4]), "cyc_raster": int(o[5]), "cyc_apply": int(o[6]), "tiles": int(o[7])}
 
     def diag_stamps(self, reset=True):
         """hs_get_diag_stamps: the 8 cycle sums a diagnostic build accumulates (tools/build_diag.py)."""
         o = np.zeros(8, np.int64)
-        check(self.L.hs_get_diag_stamps(self.h, _fp(o), 1 if reset else 0), "hs_get_diag_stamps")
+        self._check(self.L.hs_get_diag_stamps(self.h, _fp(o), 1 if reset else 0), "hs_get_diag_stamps")
         return o
 
     def stream_handle(self) -> int:
         return int(self.L.hs_get_stream(self.h) or 0)
 
     def set_timing(self, enable: bool):
-        check(self.L.hs_set_timing(self.h, 1 if enable else 0), "hs_set_timing")
+        self._check(self.L.hs_set_timing(self.h, 1 if enable else 0), "hs_set_timing")
 
     def kernel_times(self, reset=True):
         ms = np.zeros(3, np.float64)
         n = np.zeros(3, np.int64)
-        check(self.L.hs_get_kernel_times(self.h, _fp(ms), _fp(n), 1 if reset else 0), "hs_get_kernel_times")
+        self._check(self.L.hs_get_kernel_times(self.h, _fp(ms), _fp(n), 1 if reset else 0), "hs_get_kernel_times")
         names = ("match", "bin", "update")  # slot 2: hs_update_kernel (default) or hs_tile_kernel (binned)
         return {k: (float(ms[i]), int(n[i])) for i, k in enumerate(names)}
 
     def set_clock_probe(self, enable: bool):
-        check(self.L.hs_set_clock_probe(self.h, 1 if enable else 0), "hs_set_clock_probe")
+        self._check(self.L.hs_set_clock_probe(self.h, 1 if enable else 0), "hs_set_clock_probe")
 
     def clock_probe(self, reset=True):
         """Effective shader clock (MHz) of the match and update kernels over the sampled workgroups'
         lifetimes since the last reset (s_memtime / s_memrealtime x 100 MHz), with the raw sums."""
         o = np.zeros(6, np.float64)
-        check(self.L.hs_get_clock_probe(self.h, _fp(o), 1 if reset else 0), "hs_get_clock_probe")
+        self._check(self.L.hs_get_clock_probe(self.h, _fp(o), 1 if reset else 0), "hs_get_clock_probe")
         out = {}
         for i, k in enumerate(("match", "update")):
             cyc, ticks, wgs = o[3 * i: 3 * i + 3]

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import Slam2dError
+from ._stage import Stage
 
 
 class PlParams(C.Structure):
@@ -63,28 +63,15 @@ def laser_scan_to_readings(ranges, range_min, range_max) -> np.ndarray:
     return np.where((r > range_min) & (r < range_max), r, -1.0)
 
 
-class PLICP:
+class PLICP(Stage):
+    _PREFIX = "pl"
+
     def __init__(self, max_pairs: int = 1, max_rays: int = 1081, params: PlParams | None = None):
         self.L = _lib.lib()
         _declare(self.L)
         self.h = C.c_void_p()
         self.params = params or default_params()
         self._check(self.L.pl_create(C.byref(self.h), max_pairs, max_rays, C.byref(self.params)), "pl_create")
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise Slam2dError(f"{what} failed with code {rc}: {self.L.pl_last_error().decode(errors='replace')}")
-
-    def close(self):
-        if self.h:
-            self.L.pl_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def icp(self, ref, sens, angle_min, angle_inc, first_guess=(0.0, 0.0, 0.0)) -> dict:
         """One sm_icp call (lesson3/src/plicp_odometry.cc:391)."""
@@ -123,10 +110,9 @@ class PLICP:
         return dict(x=np.array(r.x[:]), valid=bool(r.valid), iterations=r.iterations, nvalid=r.nvalid, error=r.error)
 
     def icp_batch_device(self, count, n, angle_min, angle_inc, d_ref, d_sens, d_guess, d_results, hip_stream=0):
-        self._check(self.L.pl_icp_batch_device(self.h, count, n, float(angle_min), float(angle_inc),
-                                               C.c_void_p(d_ref), C.c_void_p(d_sens), C.c_void_p(d_guess or None),
-                                               C.c_void_p(d_results), C.c_void_p(hip_stream or None)),
-                    "pl_icp_batch_device")
+        self._check(self.L.pl_icp_batch_device(self.h, count, n, float(angle_min), float(angle_inc), C.c_void_p(d_ref),
+                                               C.c_void_p(d_sens), C.c_void_p(d_guess or None), C.c_void_p(d_results),
+                                               C.c_void_p(hip_stream or None)), "pl_icp_batch_device")
 
     def set_timing(self, on: bool):
         self._check(self.L.pl_set_timing(self.h, 1 if on else 0), "pl_set_timing")
@@ -134,5 +120,6 @@ class PLICP:
     def kernel_times(self, reset=True):
         ms = C.c_double()
         n = C.c_int64()
-        self._check(self.L.pl_get_kernel_times(self.h, C.byref(ms), C.byref(n), 1 if reset else 0), "pl_get_kernel_times")
+        self._check(self.L.pl_get_kernel_times(self.h, C.byref(ms), C.byref(n), 1 if reset else 0),
+                    "pl_get_kernel_times")
         return ms.value, n.value

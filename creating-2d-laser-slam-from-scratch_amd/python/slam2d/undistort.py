@@ -17,6 +17,7 @@ from collections import deque
 import numpy as np
 
 from . import _lib
+from ._stage import Stage, dp, hp
 from .hector import HsLaser
 
 UD_SCAN_OK, UD_SCAN_WAIT_IMU, UD_SCAN_WAIT_ODOM = 0, 1, 2
@@ -49,11 +50,6 @@ def _L():
     return L
 
 
-def _check(rc: int, what: str) -> None:
-    if rc != 0:
-        raise _lib.Slam2dError(f"{what} failed with code {rc}: {_L().ud_last_error().decode(errors='replace')}")
-
-
 def _dev(x):
     """A device address from an int, a torch tensor (data_ptr) or None."""
     if x is None:
@@ -63,15 +59,13 @@ def _dev(x):
     return C.c_void_p(int(x) or None)
 
 
-def _hp(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
-
-
 def rpy_from_quaternion(q) -> np.ndarray:
     """tf::Matrix3x3(q).getRPY of q = (x, y, z, w) through the library (ud_rpy_from_quaternion)."""
     qa = np.ascontiguousarray(q, np.float64).reshape(4)
     out = np.zeros(3, np.float64)
-    _check(_L().ud_rpy_from_quaternion(_hp(qa), _hp(out)), "ud_rpy_from_quaternion")
+    ud = UndistortFleet.__new__(UndistortFleet)  # the call takes no context: the library and the prefix are enough
+    ud.L = _L()
+    ud._check(ud.L.ud_rpy_from_quaternion(hp(qa), hp(out)), "ud_rpy_from_quaternion")
     return out
 
 
@@ -82,26 +76,17 @@ def default_laser(n_beams: int, angle_min: float = 0.0, angle_increment: float =
     return laser
 
 
-class UndistortFleet:
+class UndistortFleet(Stage):
     """num_streams scanners of n_beams ranges each (ud_ctx)."""
+
+    _PREFIX = "ud"
 
     def __init__(self, num_streams: int = 1, n_beams: int = 1081, max_imu: int = UD_MAX_IMU):
         self.L = _L()
         self.B, self.n, self.max_imu = int(num_streams), int(n_beams), int(max_imu)
         h = C.c_void_p()
-        _check(self.L.ud_create(C.byref(h), self.B, self.n, self.max_imu), "ud_create")
+        self._check(self.L.ud_create(C.byref(h), self.B, self.n, self.max_imu), "ud_create")
         self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.ud_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_scan_geometry(self, angle_min: float, angle_increment: float, range_min: float, range_max: float,
                           unit_vectors=None):
@@ -111,14 +96,14 @@ class UndistortFleet:
             uv = np.ascontiguousarray(unit_vectors, np.float64).reshape(-1)
             if uv.size != 2 * self.n:
                 raise ValueError("unit_vectors must be [n_beams, 2]")
-        _check(self.L.ud_set_scan_geometry(self.h, angle_min, angle_increment, range_min, range_max, _hp(uv)),
-               "ud_set_scan_geometry")
+        self._check(self.L.ud_set_scan_geometry(self.h, angle_min, angle_increment, range_min, range_max,
+                                                hp(uv) if uv is not None else None), "ud_set_scan_geometry")
 
     def set_container_rules(self, laser: HsLaser, scale_to_map: float):
-        _check(self.L.ud_set_container_rules(self.h, C.byref(laser), scale_to_map), "ud_set_container_rules")
+        self._check(self.L.ud_set_container_rules(self.h, C.byref(laser), scale_to_map), "ud_set_container_rules")
 
     def set_sources(self, use_imu: bool, use_odom: bool):
-        _check(self.L.ud_set_sources(self.h, int(bool(use_imu)), int(bool(use_odom))), "ud_set_sources")
+        self._check(self.L.ud_set_sources(self.h, int(bool(use_imu)), int(bool(use_odom))), "ud_set_sources")
 
     def stream_handle(self) -> int:
         return int(self.L.ud_get_stream(self.h) or 0)
@@ -127,11 +112,11 @@ class UndistortFleet:
                        d_imu_n=None, d_odom=None, d_cloud=None, cloud_stride: int = 0, d_xy=None, xy_stride: int = 0,
                        d_n=None, d_origo=None, d_status=None, hip_stream: int = 0):
         """ud_correct_batch_device; every buffer is a device address (int) or a torch tensor, outputs may be None."""
-        _check(self.L.ud_correct_batch_device(self.h, int(count), _dev(d_ranges), int(range_stride), _dev(d_scan_time),
-                                              _dev(d_imu), int(imu_stride), _dev(d_imu_n), _dev(d_odom), _dev(d_cloud),
-                                              int(cloud_stride), _dev(d_xy), int(xy_stride), _dev(d_n), _dev(d_origo),
-                                              _dev(d_status), C.c_void_p(hip_stream or None)),
-               "ud_correct_batch_device")
+        self._check(self.L.ud_correct_batch_device(self.h, int(count), _dev(d_ranges), int(range_stride),
+                                                   _dev(d_scan_time), _dev(d_imu), int(imu_stride), _dev(d_imu_n),
+                                                   _dev(d_odom), _dev(d_cloud), int(cloud_stride), _dev(d_xy),
+                                                   int(xy_stride), _dev(d_n), _dev(d_origo), _dev(d_status),
+                                                   dp(hip_stream)), "ud_correct_batch_device")
 
     def correct(self, ranges, scan_time_start: float, scan_time_increment: float, imu=None, odom=None) -> dict:
         """ud_correct: one scan from host arrays.  imu [k, 4] (t, wx, wy, wz), odom [2, 7]
@@ -145,9 +130,9 @@ class UndistortFleet:
         xy = np.zeros((self.n, 2), np.float32)
         origo = np.zeros(2, np.float32)
         n, st = C.c_int(), C.c_int()
-        _check(self.L.ud_correct(self.h, _hp(r), scan_time_start, scan_time_increment, _hp(im) if len(im) else None,
-                                 len(im), _hp(od), _hp(cloud), _hp(xy), C.byref(n), _hp(origo), C.byref(st)),
-               "ud_correct")
+        self._check(self.L.ud_correct(self.h, hp(r), scan_time_start, scan_time_increment, hp(im) if len(im) else None,
+                                      len(im), hp(od) if od is not None else None, hp(cloud), hp(xy), C.byref(n),
+                                      hp(origo), C.byref(st)), "ud_correct")
         return {"status": st.value, "cloud": cloud, "xy": xy[: n.value].copy(), "n": n.value, "origo": origo}
 
 

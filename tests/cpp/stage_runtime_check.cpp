@@ -4,7 +4,8 @@
 //
 //   stage_runtime_check poison [VALUE]   SLAM2D_POISON=VALUE (absent: unset) through poison_from_env
 //   stage_runtime_check epoch N          the edit epoch of a context of N graphs, step by step
-//   stage_runtime_check codes            the shared status codes and those of the seven public headers
+//   stage_runtime_check codes            the shared status codes and those of eleven public headers (the four
+//                                        oldest have the first five)
 // stdout: one JSON object.
 #include <climits>
 #include <cstdio>
@@ -12,13 +13,17 @@
 #include <cstring>
 
 #include "karto_graph_mirror.h"
+#include "slam2d/gmapping.h"
+#include "slam2d/hector.h"
 #include "slam2d/karto.h"
 #include "slam2d/karto_edit.h"
 #include "slam2d/karto_grid.h"
 #include "slam2d/karto_link.h"
 #include "slam2d/karto_loop.h"
 #include "slam2d/karto_process.h"
+#include "slam2d/plicp.h"
 #include "slam2d/spa.h"
+#include "slam2d/undistort.h"
 #include "stage_runtime.h"
 
 using namespace s2d;
@@ -31,6 +36,10 @@ S2D_ASSERT_STATUS_CODES(KL);
 S2D_ASSERT_STATUS_CODES(KE);
 S2D_ASSERT_STATUS_CODES(KP);
 S2D_ASSERT_STATUS_CODES(KD);
+S2D_ASSERT_COMMON_CODES(HS);
+S2D_ASSERT_COMMON_CODES(GM);
+S2D_ASSERT_COMMON_CODES(PL);
+S2D_ASSERT_COMMON_CODES(UD);
 
 static int run_poison(const char *value)
 {
@@ -88,6 +97,15 @@ static int run_codes()
     printf("{\"s2d\": [%d, %d, %d, %d, %d, %d]", shared[0], shared[1], shared[2], shared[3], shared[4], shared[5]);
     for (const auto &m : all)
         printf(", \"%s\": [%d, %d, %d, %d, %d, %d]", m.name, m.v[0], m.v[1], m.v[2], m.v[3], m.v[4], m.v[5]);
+    const struct {
+        const char *name;
+        int v[5];
+    } common[] = {{"hs", {HS_OK, HS_EINVAL, HS_EHIP, HS_ENOMEM, HS_ENODEV}},
+                  {"gm", {GM_OK, GM_EINVAL, GM_EHIP, GM_ENOMEM, GM_ENODEV}},
+                  {"pl", {PL_OK, PL_EINVAL, PL_EHIP, PL_ENOMEM, PL_ENODEV}},
+                  {"ud", {UD_OK, UD_EINVAL, UD_EHIP, UD_ENOMEM, UD_ENODEV}}};
+    for (const auto &m : common)
+        printf(", \"%s\": [%d, %d, %d, %d, %d]", m.name, m.v[0], m.v[1], m.v[2], m.v[3], m.v[4]);
     printf("}\n");
     return 0;
 }

@@ -2,7 +2,9 @@
 tests pin it for the others): a call sequence run once on the context's own stream and once with alternate calls on
 a torch.cuda.Stream() gives bit-identical results, equal to the plain references the stages' own tests use
 (tests/ref/spa2d_ref.py, tests/ref/karto_loop_plain.py); a context closes with its last call still pending; a context
-created, closed and created again works as the first (csrc/stage_runtime.h: StreamCall, DeviceBuffers)."""
+created, closed and created again works as the first (csrc/stage_runtime.h: StreamCall, DeviceBuffers).  And for the
+four oldest contexts (hs_, gm_, pl_, ud_), which share that runtime too: what the kernel timer counts per call, on
+every launch path, and the same lifetime."""
 import os
 import sys
 
@@ -20,7 +22,11 @@ from slam2d import karto_link as ke  # noqa: E402
 from slam2d import karto_loop as kl  # noqa: E402
 from slam2d import karto_process as kp  # noqa: E402
 from slam2d import spa as sp  # noqa: E402
+from slam2d.gmapping import GMappingFleet  # noqa: E402
+from slam2d.hector import HectorFleet  # noqa: E402
 from slam2d.karto import KtLaser  # noqa: E402
+from slam2d.plicp import PLICP  # noqa: E402
+from slam2d.undistort import UndistortFleet  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -280,3 +286,179 @@ def test_context_created_closed_and_created_again(gpu):
         b = cls(*args)
         assert b.h
         b.close()
+
+
+# ------------------------------------------------------------------------------------------------ hs_
+HS_KNOBS = ("SLAM2D_UPDATE", "SLAM2D_UPD_KERNEL", "SLAM2D_PARTS", "SLAM2D_PIPELINE", "SLAM2D_UPD_RAYS_LDS")
+HS_N = 3  # steps
+
+
+def hs_fleet(streams=2, size=64, levels=2, points=32):
+    f = HectorFleet(streams, 0.05, size, (0.5, 0.5), levels, max_points=points)
+    f.set_thresholds(-1.0, -1.0)  # every step updates the maps
+    return f
+
+
+def hs_scan(streams, points, radius):
+    """A ring of end points around every stream's origin, in map scale (cells of level 0), on the device."""
+    import torch
+
+    a = 2.0 * np.pi * np.arange(points) / points
+    xy = np.stack([radius * np.cos(a), radius * np.sin(a)], axis=1).astype(np.float32)
+    d_xy = torch.from_numpy(np.tile(xy, (streams, 1, 1))).cuda()
+    d_n = torch.full((streams,), points, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    return xy, d_xy, d_n
+
+
+def hs_steps(f, streams, points, radius, n=HS_N):
+    _, d_xy, d_n = hs_scan(streams, points, radius)
+    for _ in range(n):
+        f.step_device(d_xy.data_ptr(), points, d_n.data_ptr())
+    return f.poses()[0]  # waits for the device
+
+
+def hs_counts(times):
+    assert list(times) == ["match", "bin", "update"]
+    assert all((ms > 0.0) == (n > 0) for ms, n in times.values()), times  # every counted launch took time
+    return tuple(n for _, n in times.values())
+
+
+@pytest.fixture
+def hs_env(monkeypatch):
+    for knob in HS_KNOBS:
+        monkeypatch.delenv(knob, raising=False)
+    return monkeypatch
+
+
+def test_hs_launch_counts_default_path(gpu, hs_env):
+    f = hs_fleet()
+    hs_steps(f, 2, 32, 10.0)  # timing is off at first: nothing is counted
+    assert hs_counts(f.kernel_times(reset=False)) == (0, 0, 0)
+    f.set_timing(True)
+    hs_steps(f, 2, 32, 10.0)
+    assert hs_counts(f.kernel_times(reset=False)) == (HS_N, 0, HS_N)
+    assert hs_counts(f.kernel_times(reset=True)) == (HS_N, 0, HS_N)  # reset returns the counts ...
+    assert hs_counts(f.kernel_times()) == (0, 0, 0)                  # ... and the next read is all zero
+    f.set_timing(False)
+    hs_steps(f, 2, 32, 10.0)
+    assert hs_counts(f.kernel_times()) == (0, 0, 0)  # timing off: the counts do not move
+    f.close()
+
+
+def test_hs_launch_counts_binned_update(gpu, hs_env):
+    hs_env.setenv("SLAM2D_UPDATE", "binned")
+    f = hs_fleet()
+    f.set_timing(True)
+    hs_steps(f, 2, 32, 10.0)
+    assert hs_counts(f.kernel_times()) == (HS_N, HS_N, HS_N)
+    f.close()
+
+
+def test_hs_launch_counts_match_only(gpu, hs_env):
+    f = hs_fleet()
+    xy, _, _ = hs_scan(1, 32, 10.0)
+    f.set_timing(True)
+    f.match(0, xy, np.zeros(3, np.float32))
+    assert hs_counts(f.kernel_times()) == (1, 0, 0)
+    f.close()
+
+
+def test_hs_launch_counts_part_streams(gpu, hs_env):
+    """128 streams in two parts on their own HIP streams: the timer's one current pair is walked across them."""
+    hs_env.setenv("SLAM2D_PARTS", "2")
+    f = hs_fleet(128, 32, 1, 16)
+    f.set_timing(True)
+    hs_steps(f, 128, 16, 5.0)
+    assert hs_counts(f.kernel_times()) == (2 * HS_N, 0, 2 * HS_N)
+    f.close()
+
+
+# ------------------------------------------------------------------------------------------------ gm_, pl_
+GM_MAP = dict(xmin=-1.6, ymin=-1.6, xmax=1.6, ymax=1.6, delta=0.05, max_range=3.0, max_urange=2.5)  # 64 x 64 cells
+
+
+def gm_run(n_calls, timing=True):
+    """4 particles, 16 beams, n_calls scans and one empty launch: (scores, (ms, launches))."""
+    import torch
+
+    f = GMappingFleet(4, max_beams=16, **GM_MAP)
+    assert f.size == (64, 64)
+    f.set_beams(2.0 * np.pi * np.arange(16) / 16)
+    f.set_timing(timing)
+    d_poses = torch.from_numpy(GMappingFleet.poses4(np.zeros((4, 3)) + 0.02 * np.arange(4)[:, None])).cuda()
+    d_ranges = torch.full((16,), 1.0, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    for _ in range(n_calls):
+        f.compute_device(d_poses.data_ptr(), d_ranges.data_ptr(), 16)
+    f.compute_device(d_poses.data_ptr(), d_ranges.data_ptr(), 16, count=0)  # launches nothing
+    out = f.scores()[0], f.kernel_times()
+    assert f.kernel_times() == (0.0, 0)  # reset is the default
+    f.close()
+    return out
+
+
+def test_gm_launch_counts(gpu):
+    scores, (ms, launches) = gm_run(3)
+    assert launches == 3 and ms > 0.0  # one count per call: the score and the compute kernel are one span
+    assert gm_run(3, timing=False)[1] == (0.0, 0)
+
+
+def pl_run(n_calls, timing=True):
+    """2 pairs of 64 rays, n_calls batches and one empty batch: (results' bytes, (ms, launches))."""
+    import torch
+
+    n = 64
+    ang = -1.0 + 2.0 * np.arange(n) / n
+    scan = np.stack([2.0 + 0.3 * np.cos(3.0 * ang), 2.5 + 0.2 * np.sin(2.0 * ang)])
+    d_ref, d_sens = torch.from_numpy(scan).cuda(), torch.from_numpy(scan + 0.01).cuda()
+    d_guess = torch.zeros((2, 3), dtype=torch.float64, device="cuda")
+    d_out = torch.zeros((2, 48), dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    f = PLICP(2, n)
+    f.set_timing(timing)
+    args = (n, ang[0], 2.0 / n, d_ref.data_ptr(), d_sens.data_ptr(), d_guess.data_ptr(), d_out.data_ptr())
+    for _ in range(n_calls):
+        f.icp_batch_device(2, *args)
+    f.icp_batch_device(0, *args)  # launches nothing
+    times = f.kernel_times()  # waits for the device
+    out = d_out.cpu().numpy().tobytes(), times
+    assert f.kernel_times() == (0.0, 0)
+    f.close()
+    return out
+
+
+def test_pl_launch_counts(gpu):
+    _, (ms, launches) = pl_run(3)
+    assert launches == 3 and ms > 0.0  # one count per batch call
+    assert pl_run(3, timing=False)[1] == (0.0, 0)
+
+
+# ------------------------------------------------------------------------------------------------ lifetime
+def closed_and_made_again(make):
+    """close() frees what the context allocated: the same context can be made again; closing twice is harmless."""
+    a = make()
+    a.close()
+    assert not a.h
+    a.close()
+    b = make()
+    assert b.h
+    return b
+
+
+def test_oldest_contexts_created_closed_and_created_again(gpu, hs_env):
+    first = hs_fleet()
+    want = hs_steps(first, 2, 32, 10.0)
+    first.close()
+    again = closed_and_made_again(hs_fleet)
+    assert hs_steps(again, 2, 32, 10.0).tobytes() == want.tobytes()
+    again.close()
+    again.close()
+    assert gm_run(2)[0].tobytes() == gm_run(2)[0].tobytes()  # each run makes and closes its own context
+    closed_and_made_again(lambda: GMappingFleet(4, max_beams=16, **GM_MAP)).close()
+    assert pl_run(1)[0] == pl_run(1)[0]
+    closed_and_made_again(lambda: PLICP(2, 64)).close()
+    ud = closed_and_made_again(lambda: UndistortFleet(2, 16, 8))
+    ud.set_scan_geometry(-1.0, 0.125, 0.1, 10.0)
+    ud.close()
+    ud.close()
