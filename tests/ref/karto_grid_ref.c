@@ -185,8 +185,9 @@ void kgr_ray_trace_cells(int width, int height, int x0, int y0, int x1, int y1, 
     }
 }
 
-/* OccupancyGrid::AddScan (Karto.h:5852-5899), doUpdate = false */
-static void kgr_add_scan(const kgr_grid *g, const kgr_laser *L, const double *ranges, const double *pose)
+/* OccupancyGrid::AddScan (Karto.h:5852-5899), doUpdate = false.  With cells != NULL nothing is traced: beam i's
+ * RayTrace arguments after WorldToGrid go to cells[5 * i ..] as x0, y0, x1, y1, isEndPointValid (-1: ignored). */
+static void kgr_add_scan(const kgr_grid *g, const kgr_laser *L, const double *ranges, const double *pose, int *cells)
 {
     const double rangeThreshold = L->range_threshold;
     const double maxRange = L->maximum_range;
@@ -196,7 +197,10 @@ static void kgr_add_scan(const kgr_grid *g, const kgr_laser *L, const double *ra
         const double rangeReading = ranges[pointIndex];
         const int isEndPointValid = rangeReading < (rangeThreshold - KT_TOLERANCE);
         double px, py;
-        if (rangeReading <= minRange || rangeReading >= maxRange || isnan(rangeReading)) continue;
+        if (rangeReading <= minRange || rangeReading >= maxRange || isnan(rangeReading)) {
+            if (cells) cells[5 * pointIndex + 4] = -1;
+            continue;
+        }
         kgr_point(L, pose, pointIndex, rangeReading, &px, &py);
         if (rangeReading >= rangeThreshold) {
             const double ratio = rangeThreshold / rangeReading;
@@ -205,8 +209,26 @@ static void kgr_add_scan(const kgr_grid *g, const kgr_laser *L, const double *ra
             px = pose[0] + ratio * dx;
             py = pose[1] + ratio * dy;
         }
-        kgr_ray_trace(g, pose[0], pose[1], px, py, isEndPointValid);
+        if (cells) {
+            int *o = cells + 5 * pointIndex;
+            kgr_world_to_grid(g, pose[0], pose[1], &o[0], &o[1]);
+            kgr_world_to_grid(g, px, py, &o[2], &o[3]);
+            o[4] = isEndPointValid;
+        } else {
+            kgr_ray_trace(g, pose[0], pose[1], px, py, isEndPointValid);
+        }
     }
+}
+
+/* what AddScan hands to TraceLine, per beam of every scan: cells holds count * n_readings * 5 ints (zeroed by the
+ * caller), see kgr_add_scan */
+void kgr_ray_cells(const kgr_laser *L, int count, const double *ranges, const double *poses, double resolution,
+                   const double *offset, int *cells)
+{
+    kgr_grid g = {0, 0, offset[0], offset[1], 1.0 / resolution, NULL, NULL};
+    for (int s = 0; s < count; s++)
+        kgr_add_scan(&g, L, ranges + (size_t)s * L->n_readings, poses + 3 * (size_t)s,
+                     cells + 5 * (size_t)s * L->n_readings);
 }
 
 /* UpdateCell (Karto.h:5953-5968) after Clear(): 0 unknown, 100 occupied, 255 free; and the byte
@@ -239,6 +261,6 @@ void kgr_create_from_scans(const kgr_laser *L, int count, const double *ranges, 
     memset(pass, 0, sizeof(uint32_t) * cells);
     memset(hits, 0, sizeof(uint32_t) * cells);
     for (int s = 0; s < count; s++)
-        kgr_add_scan(&g, L, ranges + (size_t)s * L->n_readings, poses + 3 * (size_t)s);
+        kgr_add_scan(&g, L, ranges + (size_t)s * L->n_readings, poses + 3 * (size_t)s, NULL);
     kgr_update(cells, pass, hits, min_pass_through, occupancy_threshold, state, ros);
 }

@@ -60,6 +60,8 @@ def lib() -> C.CDLL:
         L.kgr_line_cells.argtypes = [i, i, i, i, p]
         L.kgr_ray_trace_cells.restype = None
         L.kgr_ray_trace_cells.argtypes = [i, i, i, i, i, i, i, p, p]
+        L.kgr_ray_cells.restype = None
+        L.kgr_ray_cells.argtypes = [C.POINTER(KgrLaser), i, p, p, d, p, p]
         _LIB = L
     return _LIB
 
@@ -74,6 +76,8 @@ def line_lib() -> C.CDLL:
         L.kglh_cells.argtypes = [i, i, i, i, p]
         L.kglh_tiled_cells.restype = i
         L.kglh_tiled_cells.argtypes = [i, i, i, i, i, p]
+        L.kglh_map_cells.restype = i
+        L.kglh_map_cells.argtypes = [i, i, i, i, i, i, i, p]
         _LINE = L
     return _LINE
 
@@ -110,6 +114,14 @@ def tiled_line(x0, y0, x1, y1, tile=64) -> np.ndarray:
     return cells[:k]
 
 
+def map_line(x0, y0, x1, y1, width, height, tile=64) -> np.ndarray:
+    """The cells kg_trace_kernel's walk adds for one ray on a width x height map (its tiles, its box cull)."""
+    cells = np.zeros((width + height, 2), np.int32)
+    k = line_lib().kglh_map_cells(x0, y0, x1, y1, tile, width, height, _hp(cells))
+    assert 0 <= k <= len(cells), k
+    return cells[:k]
+
+
 def ray_trace_cells(width, height, x0, y0, x1, y1, end_valid):
     """RayTrace between two cells on an empty width x height grid: (pass, hits) [height, width]."""
     ps = np.zeros((height, width), np.uint32)
@@ -140,6 +152,19 @@ def create_from_scans(case: dict) -> dict:
     sh = (h, w)
     return {"width": w, "height": h, "offset": off, "pass": ps[: w * h].reshape(sh), "hits": ht[: w * h].reshape(sh),
             "state": st[: w * h].reshape(sh), "ros": ro[: w * h].reshape(sh)}
+
+
+def ray_cells(case: dict, e: dict) -> np.ndarray:
+    """What the restatement's AddScan hands to TraceLine on the map e = create_from_scans(case):
+    [scans, beams, 5] ints x0, y0, x1, y1, isEndPointValid (-1: the beam is ignored)."""
+    lz = _kgr_laser(case["laser"])
+    n = int(case["laser"]["n_readings"])
+    r = np.ascontiguousarray(case["ranges"], np.float64).reshape(-1, n)
+    p = np.ascontiguousarray(case["poses"], np.float64).reshape(-1, 3)
+    off = np.ascontiguousarray(e["offset"], np.float64)
+    cells = np.zeros((r.shape[0], n, 5), np.int32)
+    lib().kgr_ray_cells(C.byref(lz), r.shape[0], _hp(r), _hp(p), float(case["resolution"]), _hp(off), _hp(cells))
+    return cells
 
 
 # ---------------------------------------------------------------------------------------------- input cases
@@ -254,6 +279,104 @@ def case_fine(seed=5) -> dict:
     """Resolution 0.01 (the matcher's): rays of several hundred cells."""
     c = case_cross(S=3, n=361, seed=seed, resolution=0.01)
     return c
+
+
+ROUNDS_FIRST = 256   # kg_trace_kernel lists the scans of a tile this many at a time (KG_THREADS)
+ROUNDS_REACH = 0.25  # m: no reading of case_rounds is longer
+
+
+def case_rounds(S=600, seed=11, one_pose=False) -> dict:
+    """More scans than one round of kg_trace_kernel's scan list (256): 7 beams of at most 0.25 m from poses spread
+    over a 6 m x 4.8 m room, the first 256 at x < -0.3 m, the others at x > 0.3 m, so that the map's right-hand tile
+    column (x >= 64 cells at resolution 0.05) is met by scans of the later rounds only.  one_pose: every scan at one
+    pose instead, whose cell then holds one increment per traced beam of every scan."""
+    rng = np.random.default_rng(seed)
+    lz = make_laser(7)
+    if one_pose:
+        poses = np.repeat(np.array([[0.37, -0.21, 0.6]]), S, axis=0)
+    else:
+        k = min(S, ROUNDS_FIRST)
+        x = np.concatenate([rng.uniform(-2.5, -0.3, k), rng.uniform(0.3, 2.5, S - k)])
+        x[0], x[S - 1] = -2.5, 2.5      # the box does not depend on the seed
+        y = rng.uniform(-1.95, 1.95, S)
+        y[0], y[S - 1] = -1.95, 1.95
+        poses = np.stack([x, y, rng.uniform(-math.pi, math.pi, S)], axis=1)
+    r = np.minimum(room_ranges(lz, poses, (0.0, 0.0), (3.0, 2.4), rng), rng.uniform(0.12, ROUNDS_REACH, (S, 7)))
+    return _case(lz, r, poses)
+
+
+LONG_RES, LONG_THR, LONG_MAX = 0.001, 45.0, 60.0
+LONG_ORIENTATIONS = ("x", "y", "slant")
+FAR_THR, FAR_MAX = 1000.0, 2000.0
+
+
+def case_long_lines(orientation="x") -> dict:
+    """Rays beyond the 32-bit path of csrc/karto_grid_line.h (more than 32767 major steps) at resolution 0.001: a
+    9-beam laser spanning 8.4 mrad, two scans looking along the major axis from near the origin and one looking
+    back from 41 m, so both end orders occur (TraceLine swaps the ends of the third scan's rays).  The centre beams
+    of the first two scans are exactly 32767 and 32768 cells long; the reading of 50 m is clipped to 45000 cells
+    and runs off the map.  'x': along +x; 'y': the same turned by pi / 2 (steep lines); 'slant': headings 4 mrad
+    off the axis, minor extents of a few hundred cells."""
+    assert orientation in LONG_ORIENTATIONS, orientation
+    lz = make_laser(9, minimum_angle=-4 * 1.05e-3, angular_resolution=1.05e-3, range_threshold=LONG_THR,
+                    maximum_range=LONG_MAX)
+    th = 4e-3 if orientation == "slant" else 0.0
+    poses = np.array([[0.0, 0.0, th], [0.02, 0.0105, th], [41.0, -0.0073, math.pi - th]])
+    r = np.array([[32.767, 33.0, 36.0, 38.0, 32.767, 40.0, 40.5, 41.0, 50.0],
+                  [32.768, 40.5, np.nan, 36.0, 32.768, 38.0, 33.0, 41.0, 32.7675],
+                  [40.5, 36.0, 32.768, 40.0, 38.0, 32.767, 33.0, 40.5, 36.0]])
+    if orientation == "y":
+        poses = np.stack([-poses[:, 1], poses[:, 0], poses[:, 2] + math.pi / 2.0], axis=1)
+    return _case(lz, r, poses, resolution=LONG_RES)
+
+
+DIMS = ((64, 64), (65, 64), (64, 65), (128, 63), (3, 5), (4, 4), (15, 1), (16, 1), (17, 1), (1, 17), (129, 1), (1, 129),
+        (63, 2), (2, 8))
+
+
+def case_dims(w, h) -> dict:
+    """A map of exactly w x h cells (resolution 0.05): three scans at (0, 0, 0) of case_thresholds' four-beam axis
+    laser whose -x / +x readings are (w // 2, w - w // 2) cells long, the -y / +y ones (h // 2, h - h // 2); a
+    reading of 0 cells becomes NaN.  A single column or row takes its one cell on the minus side, so the scans' own
+    cell lies one past it (ox == width, oy == height): the rays along the other axis run wholly off the map."""
+    assert w >= 1 and h >= 1 and (w, h) != (1, 1)
+    lz = make_laser(4, minimum_angle=0.0, angular_resolution=math.pi / 2.0, minimum_range=0.001)
+    cell = 0.05
+
+    def pair(n):
+        lo, hi = (1, 0) if n == 1 else (n // 2, n - n // 2)
+        return [k * cell if k else np.nan for k in (hi, lo)]
+
+    (xp, xm), (yp, ym) = pair(w), pair(h)
+    return _case(lz, np.repeat(np.array([[xp, yp, xm, ym]]), 3, axis=0), np.zeros((3, 3)))
+
+
+BEAMS = (1, 64, 256, 257, 1025, 4096)
+
+
+def case_beams(n, seed=13) -> dict:
+    """Two scans of n beams in a small room: n at and around the strides of the kernels' beam loops (256; 4 x 64 in
+    kg_trace_kernel) and the largest kg_create admits.  n = 1: a laser whose only beam looks along the heading."""
+    rng = np.random.default_rng(seed)
+    lz = make_laser(n, minimum_angle=0.0) if n == 1 else make_laser(n)
+    poses = np.array([[0.0, 0.0, 0.0], [0.5, -0.5, math.pi / 2.0]])
+    return _case(lz, room_ranges(lz, poses, (0.0, 0.0), (2.9, 2.3), rng), poses)
+
+
+def case_far_ends() -> dict:
+    """Products beyond 32 bits.  The rays of case_long_lines are at most 45000 cells long, and 2 * 45000^2 < 2^32:
+    their 64-bit divisions would also come out right in 32 bits.  Here range_threshold is 10^6 cells (resolution
+    0.001; kg_create admits 2^20) and readings of 1500 m are clipped to it, at 0.1 rad + k * 45 degrees, from two
+    scans at opposite corners of a map of about 3400 x 3300 cells with headings 0 and pi: the clipped rays cross
+    the whole map towards (+, +) and towards (-, -) and end far off it, and on the map 2 * i * deltaY exceeds 2^32.
+    Two short readings per scan score hits."""
+    lz = make_laser(8, minimum_angle=0.1, angular_resolution=math.pi / 4.0, range_threshold=FAR_THR,
+                    maximum_range=FAR_MAX)
+    poses = np.array([[0.0, 0.0, 0.0], [3.4007, 3.3002, math.pi]])
+    r = np.full((2, 8), 1500.0)
+    r[:, 0], r[:, 7], r[:, 3] = 1.7, 0.9, np.nan
+    r[:, 2] = 1200.0                           # clipped with another ratio
+    return _case(lz, r, poses, resolution=LONG_RES)
 
 
 def golden_cases() -> dict:

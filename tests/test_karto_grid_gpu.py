@@ -305,3 +305,144 @@ def test_fine_resolution_long_rays(gpu, split):
     b = _builder(c, want=want)
     R.assert_maps_equal(b.create_from_scans(c["ranges"], c["poses"]), want)
     b.close()
+
+
+# ------------------------------------------------------------------ directed cases (tests/ref/karto_grid_ref.py; that
+# each takes the path it is named for is asserted without a GPU in tests/test_karto_grid_cpu.py)
+CASES.update({f"rounds{S}": functools.partial(R.case_rounds, S) for S in (257, 513, 600)})
+CASES["rounds600_one_pose"] = functools.partial(R.case_rounds, 600, one_pose=True)
+CASES.update({f"dims{w}x{h}": functools.partial(R.case_dims, w, h) for w, h in R.DIMS})
+CASES.update({f"beams{n}": functools.partial(R.case_beams, n) for n in R.BEAMS})
+
+
+@functools.lru_cache(maxsize=1)
+def _want_long(orientation):
+    """The restatement's map of a long-line case; one at a time (13 M cells, 130 MB of planes)."""
+    c = R.case_long_lines(orientation)
+    return c, R.create_from_scans(c)
+
+
+def _set_split(monkeypatch, value):
+    if value == "auto":
+        monkeypatch.delenv("SLAM2D_KG_SPLIT", raising=False)
+    else:
+        monkeypatch.setenv("SLAM2D_KG_SPLIT", value)
+    return value
+
+
+@pytest.fixture(params=["auto", "1", "2", "3", "32"])
+def split5(request, monkeypatch):
+    """`split`, and also two parts (more than 256 scans per part at 513 and 600 scans) and the largest split, 32
+    (a short last part at 600 scans, empty parts at 513 and 257)."""
+    return _set_split(monkeypatch, request.param)
+
+
+@pytest.fixture(params=["auto", "3"])
+def split_auto3(request, monkeypatch):
+    return _set_split(monkeypatch, request.param)
+
+
+@pytest.mark.parametrize("S", [257, 513, 600])
+def test_scan_list_rounds(gpu, split5, S):
+    """More scans than kg_trace_kernel lists in one round, and than kg_bbox_reduce_kernel takes in one step; the
+    map's right-hand tile column is met by scans of the later rounds only."""
+    c, want = _want(f"rounds{S}")
+    assert len(c["poses"]) == S > 256 and want["width"] > 64 and want["pass"][:, 64:].sum() > 0
+    b = _builder(c, want=want)
+    _check_build(b, c, want)
+    b.close()
+
+
+def test_600_scans_at_one_pose(gpu, split5):
+    c, want = _want("rounds600_one_pose")
+    b = _builder(c, want=want)
+    got = _check_build(b, c, want)
+    b.close()
+    ox, oy = R.ray_cells(c, want)[0, 0, :2]
+    assert got["pass"][oy, ox] == 600 * c["laser"]["n_readings"] == got["pass"].max()
+
+
+@pytest.mark.parametrize("order", ["shuffled", "halves_swapped"])
+def test_scan_order_invariance(gpu, monkeypatch, order):
+    """The planes do not depend on the order of the scans (and so not on which round or part lists a scan):
+    device against device, under the library's split rule and with one owner per tile."""
+    c, want = _want("rounds600")
+    S = len(c["poses"])
+    perm = np.random.default_rng(17).permutation(S) if order == "shuffled" else np.r_[256:512, 0:256, 512:S]
+    assert sorted(perm.tolist()) == list(range(S)) and perm[0] != 0
+    maps = []
+    for value in ("auto", "1"):
+        _set_split(monkeypatch, value)
+        b = _builder(c, want=want)
+        _poison(b)
+        maps.append(b.create_from_scans(c["ranges"], c["poses"]))
+        _poison(b)
+        maps.append(b.create_from_scans(c["ranges"][perm], c["poses"][perm]))
+        b.close()
+    for m in maps[1:]:
+        R.assert_maps_equal(m, maps[0])
+    assert maps[0]["pass"].sum() > 0
+
+
+@pytest.mark.parametrize("orientation,value", [("x", "auto"), ("x", "1"), ("x", "3"), ("y", "auto"), ("slant", "auto")])
+def test_long_lines_64bit_path(gpu, monkeypatch, orientation, value):
+    """Rays of 32767, 32768 and up to 45000 major steps at resolution 0.001: the 64-bit division of
+    csrc/karto_grid_line.h's clip, carry and error as device code, in both end orders."""
+    _set_split(monkeypatch, value)
+    c, want = _want_long(orientation)
+    assert want["width"] * want["height"] <= 1 << 24 and max(want["width"], want["height"]) > 40000
+    b = _builder(c, want=want)
+    _check_build(b, c, want)
+    b.close()
+
+
+@pytest.mark.parametrize("value", ["auto", "3"])
+def test_far_ends_64bit_products(gpu, monkeypatch, value):
+    """Clipped rays of 10^6 cells (kg_create admits 2^20) across a 3401 x 4440 map: on the map's own cells
+    2 * i * deltaY + deltaX exceeds 2^32, which no ray of the long-line cases reaches (2 * 45000^2 < 2^32), so
+    only here would a 32-bit division in the device's clip, carry or error show."""
+    _set_split(monkeypatch, value)
+    c = R.case_far_ends()
+    want = R.create_from_scans(c)
+    assert (want["width"], want["height"]) == (3401, 4440) and want["hits"].sum() > 0
+    b = _builder(c, want=want)
+    _check_build(b, c, want)
+    b.close()
+
+
+@pytest.mark.parametrize("w,h", R.DIMS)
+def test_map_dimensions(gpu, split_auto3, w, h):
+    """Maps of fewer than 16 cells, of exactly one group of 16, of whole tiles, with a tile one cell wide or
+    high, single rows and columns (the scans' own cell then lies off the map)."""
+    c, want = _want(f"dims{w}x{h}")
+    assert (want["width"], want["height"]) == (w, h) and want["pass"].sum() > 0
+    b = _builder(c, want=want)
+    _check_build(b, c, want)
+    b.close()
+    b = _builder(c, max_cells=w * h)   # exactly enough: the planes end with the map (rounded up to 16 cells)
+    _check_build(b, c, want)
+    b.close()
+
+
+@pytest.mark.parametrize("n", R.BEAMS)
+def test_beam_counts(gpu, monkeypatch, n):
+    _set_split(monkeypatch, "auto")
+    c, want = _want(f"beams{n}")
+    assert c["laser"]["n_readings"] == n
+    b = _builder(c, want=want)
+    _check_build(b, c, want)
+    b.close()
+
+
+def test_back_to_back_600_5_600(gpu, split):
+    """One context for 600 scans: 600, then the first 5 of them, then the 600 again.  Nothing of the larger
+    build's scan records, ray words or planes may survive into the smaller one."""
+    c, want = _want("rounds600")
+    c5 = dict(c, ranges=c["ranges"][:5].copy(), poses=c["poses"][:5].copy())
+    want5 = R.create_from_scans(c5)
+    assert 0 < want5["width"] * want5["height"] < want["width"] * want["height"]
+    b = _builder(c, max_scans=600, want=want)
+    _check_build(b, c, want)
+    _check_build(b, c5, want5)
+    _check_build(b, c, want)
+    b.close()
